@@ -8,8 +8,14 @@ process per GPU) each rank hashes its own batch (message batches shard with no c
 ``scaling`` = "weak"), and ``value`` = all records hashed / max-over-ranks wall time.
 
 Also reported on the same line: ``roofline`` (the hash kernel's VALU roofline fraction,
-kernel time from HIP events on the launch stream) and ``cpu_baseline`` (the oracle's C
-restatement on this host's cores, rank 0 at N=1 only).
+kernel time from HIP events on the launch stream around the same timed steps).
+
+A plain run (``--gpus N --steps K --warmup W``) does only that: set up, warm up, time the K
+steps, write the last step's digests if ``--dump-outputs DIR`` is given, print the line.
+``--full`` adds, after the timed steps, everything else the line can hold: the digests'
+check against the C port (``parity``), ``host_api``, ``cpu_baseline`` (the oracle's C
+restatement on this host's cores, rank 0 at N=1 only) and the epoch, replay, wire, attcheck,
+wire_att and shuffle legs, each with its own checker, roofline and CPU baseline.
 """
 import argparse
 import ctypes
@@ -41,6 +47,25 @@ HBM_PEAK = 8.0e12                  # B/s (spec)
 REL_COST = {"v_lshl_add_u64": 1 / 0.304, "v_xor_b32": 1.0, "v_alignbit_b32": 1 / 0.602}
 SLOTS_PER_G = 6 * REL_COST["v_lshl_add_u64"] + 8 * REL_COST["v_xor_b32"] + 6 * REL_COST["v_alignbit_b32"]
 OPS_PER_COMPRESSION = 96 * SLOTS_PER_G + 32            # ~3652 full-rate slots
+
+
+DUMP_MAX_RECORDS = 1 << 18  # rows of --dump-outputs' digests.npy: 32 MiB as float32 (+ 2 MiB of record numbers)
+
+
+def dump_outputs(path, d_out, n, rank):
+    """``--dump-outputs``: the digests the last timed step wrote (what a caller of
+    pz_dev_blake2b512_fixed receives), as float32 rows of 32 byte values.  Up to
+    DUMP_MAX_RECORDS records all of them; above that a fixed sample (seed 0, independent of
+    the rank and of the run) of that many, in ascending record order, with the record numbers
+    beside them.  Rank 0 writes ``digests*.npy``, rank r > 0 ``digests*_rank<r>.npy``."""
+    os.makedirs(path, exist_ok=True)
+    tag = "" if rank == 0 else "_rank%d" % rank
+    got = d_out.cpu().numpy().reshape(n, 32)
+    if n > DUMP_MAX_RECORDS:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=DUMP_MAX_RECORDS, replace=False))
+        got = got[idx]
+        np.save(os.path.join(path, "digests_index%s.npy" % tag), idx.astype(np.float64))
+    np.save(os.path.join(path, "digests%s.npy" % tag), got.astype(np.float32))
 
 
 def warm_clocks(step, torch, dev, ms):
@@ -87,6 +112,16 @@ def parse():
                    help="untimed back-to-back launches before the warmup steps: MI355X clocks ramp "
                         "from idle over ~100 launches of this kernel (tools/hash_steady.py)")
     p.add_argument("--records", type=int, default=1 << 20)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline's timed steps, also run everything else the line can report: the "
+                        "digests' check against the C port, host_api, the CPU baselines, and the epoch, replay, "
+                        "wire, attcheck, wire_att and shuffle legs (the --no-*, --epoch-* and --replay-* options "
+                        "select among these and mean nothing without --full)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the digests the last timed step left in the output buffer "
+                        "to DIR/digests.npy (float32, one row of 32 byte values per record; above %d records a "
+                        "fixed seeded sample of that many rows, their record numbers in DIR/digests_index.npy)"
+                        % DUMP_MAX_RECORDS)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                    help="collective backend at N > 1 (gloo: rehearsal with ranks sharing a GPU)")
@@ -1430,16 +1465,22 @@ def main():
     if world > 1:
         wall = max_over_ranks(wall, torch, dist, dev)
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out, n, rank)
+
+    # A plain run ends here with the headline's line; everything below that measures or checks
+    # anything else runs only under --full.
+    full = args.full
     # the checker at N > 1 (and at N = 1 without the cpu_baseline leg, whose full-batch check
     # it replaces): this rank's first and last 65,536 digests against the C port
     spot = None
-    if world > 1 or args.no_cpu_baseline:
+    if full and (world > 1 or args.no_cpu_baseline):
         ok, what = hash_spot_check(recs, d_out)
         spot = "%s%s vs the C port (oracle/c/blake2b_ref.c): %s" % (
             what, "" if world == 1 else " of every rank", ok if world == 1 else all_ranks(ok, torch, dist, dev))
 
     comm = None
-    if world > 1 and not args.no_epoch:
+    if full and world > 1 and not args.no_epoch:
         # every rank must take the same path: agree on whether the communicator came up; a
         # failure ends the run (non-zero exit), it never switches to another path
         err = None
@@ -1454,19 +1495,19 @@ def main():
                   % (rank, err or "another rank failed"), file=sys.stderr, flush=True)
             dist.destroy_process_group()
             sys.exit(3)
-    epoch = None if args.no_epoch else epoch_leg(args, torch, dist, dev, rank, world, comm=comm)
+    epoch = None if (args.no_epoch or not full) else epoch_leg(args, torch, dist, dev, rank, world, comm=comm)
     # configs[3]'s instance size (1,048,576 validators) on this one GPU: the N = 1 point of
     # the 1/2/4/8-GPU series that the N > 1 epoch leg runs (16 instances per GPU per step)
     epoch_1m = None
     if epoch is not None and world == 1 and not args.epoch_validators:
         epoch_1m = epoch_leg(args, torch, dist, dev, rank, world, nval=1 << 20, ninst=16, baseline=False)
-    replay = None if args.no_replay else replay_leg(args, torch, dist, dev, rank, world)
+    replay = None if (args.no_replay or not full) else replay_leg(args, torch, dist, dev, rank, world)
     replay_sh = (replay_sharded_leg(args, torch, dist, dev, rank, world, comm)
                  if (world > 1 and comm is not None and not args.no_replay) else None)
-    wire_out = None if args.no_wire else wire_leg(args, torch, dist, dev, rank, world)
-    att_out = None if args.no_attcheck else attcheck_leg(args, torch, dist, dev, rank, world)
-    watt_out = None if args.no_wire else wire_att_leg(args, torch, dist, dev, rank, world, d_out)
-    shuf = shuffle_leg(args) if (rank == 0 and not args.no_epoch) else None
+    wire_out = None if (args.no_wire or not full) else wire_leg(args, torch, dist, dev, rank, world)
+    att_out = None if (args.no_attcheck or not full) else attcheck_leg(args, torch, dist, dev, rank, world)
+    watt_out = None if (args.no_wire or not full) else wire_att_leg(args, torch, dist, dev, rank, world, d_out)
+    shuf = shuffle_leg(args) if (full and rank == 0 and not args.no_epoch) else None
 
     if rank == 0:
         total = n * world * args.steps
@@ -1508,10 +1549,10 @@ def main():
                              "peak_GBps": HBM_PEAK / 1e9},
             },
         }
-        if world == 1:
+        if full and world == 1:
             line["host_api"] = host_api_rate(recs)
         line["host"] = host_info()
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             cb, digests = cpu_baseline(recs)
             line["cpu_baseline"] = cb
             if digests is not None:  # the checker: GPU digests of the timed batch vs the C port
@@ -1551,7 +1592,7 @@ def main():
     if comm is not None:
         comm.free()
     if rank == 0:
-        if world > 1 and args.backend == "nccl" and not args.no_single_process_leg:
+        if full and world > 1 and args.backend == "nccl" and not args.no_single_process_leg:
             # the other ranks have left the process group (and exit); rank 0 runs the
             # one-process form over all the node's GPUs in a child process with a time limit
             del d_in, d_out

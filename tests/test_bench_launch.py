@@ -53,7 +53,7 @@ def test_rank_failure_is_the_exit_code():
 
 @pytest.mark.gpu
 def test_bench_world2_gloo_rehearsal():
-    r = _run(["--gpus", "2", "--backend", "gloo", "--no-cpu-baseline", "--records", "4096", "--replay-blocks", "130",
+    r = _run(["--gpus", "2", "--backend", "gloo", "--full", "--no-cpu-baseline", "--records", "4096", "--replay-blocks", "130",
               "--steps", "2", "--warmup", "1", "--clock-warm-ms", "0", "--epoch-validators", "65536",
               "--epoch-instances", "4", "--no-wire", "--no-attcheck"], 600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -61,6 +61,36 @@ def test_bench_world2_gloo_rehearsal():
     assert line["n_gpus"] == 2 and line["launch"].startswith("torchrun child")
     assert line["epoch"]["config"]["path_note"].startswith("gloo rehearsal")
     assert line["replay"]["processed"] == 130 * 2 // 2  # blocks per rank (every block processed)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_digests(tmp_path):
+    """A plain run prints the headline line alone (no leg, checker or CPU baseline: those are
+    ``--full``'s), times exactly ``--steps`` steps, and ``--dump-outputs`` writes the digests of
+    the last timed step: every record's when the batch is small, BLAKE2b-512[:32] by hashlib."""
+    import hashlib
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    from prysm_amd import synth
+
+    n = 4099
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--clock-warm-ms", "0", "--records", str(n),
+              "--dump-outputs", str(tmp_path / "out")], 300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    (line,) = _json_lines(r.stdout)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["unit"] == "hashes/s"
+    assert abs(line["value"] - n / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    moved = ("epoch", "epoch_1m_single_gpu", "replay", "wire", "attcheck", "wire_att", "shuffle", "host_api",
+             "cpu_baseline", "parity")
+    assert not [k for k in moved if k in line]
+    assert sorted(os.listdir(tmp_path / "out")) == ["digests.npy"]
+    got = np.load(tmp_path / "out" / "digests.npy")
+    assert got.dtype == np.float32 and got.shape == (n, 32)
+    recs = synth.attestation_records_512(n, seed=2)
+    want = np.array([list(hashlib.blake2b(m.tobytes()).digest()[:32]) for m in recs], dtype=np.float32)
+    assert np.array_equal(got, want)
 
 
 @pytest.mark.gpu

@@ -7,7 +7,7 @@
 #   tests      pytest -m gpu (PYTEST_K: a -k expression; PYTEST_FILES: test paths)
 #   abtests    pytest -m ab (the A/B library's forms)
 #   smoke      __graft_entry__.smoke()
-#   bench      python bench.py $BENCH_ARGS               -> $O/bench.json (the JSON line)
+#   bench      python bench.py --full $BENCH_ARGS        -> $O/bench.json (the JSON line, every leg)
 #   prof       rocprofv3 --kernel-trace --stats of a short bench run -> $O/prof/
 #   pmc:W      counter passes (bytes) over tools/pmc_workload.py's workload W -> $O/pmc_W/summary.json
 #   pmcfull:W  the same plus the SQ and GRBM passes
@@ -35,14 +35,14 @@ run_smoke() {
   tail -1 "$O/smoke.txt"
 }
 run_bench() {
-  timeout -k 10 ${BENCH_TIMEOUT:-500} python -u bench.py $BENCH_ARGS > "$O/bench.out" 2> "$O/bench.err" \
+  timeout -k 10 ${BENCH_TIMEOUT:-500} python -u bench.py --full $BENCH_ARGS > "$O/bench.out" 2> "$O/bench.err" \
     || { echo "BENCH_FAIL"; tail -30 "$O/bench.err"; exit 14; }
   grep '^{' "$O/bench.out" | tail -1 > "$O/bench.json"
   python3 tools/bench_summary.py "$O/bench.json"
 }
 run_prof() {
   (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run \
-    --output-format csv -- python3 "$R/bench.py" --steps 10 --warmup 2 --no-cpu-baseline ${PROF_ARGS} \
+    --output-format csv -- python3 "$R/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline ${PROF_ARGS} \
     > "$O/prof.log" 2>&1) || { echo "PROF_FAIL"; tail -20 "$O/prof.log"; exit 15; }
   echo "prof ok"
 }

@@ -14,7 +14,7 @@ else
   for w in epoch65k_cold epoch1m_cold epoch65k epoch1m; do
     bash tools/gpu_pmc.sh ${T}/pmc_$w $w bytes || exit 22
   done
-  timeout -k 10 700 python -u bench.py --gpus 2 --backend gloo --steps 5 --warmup 2 > "$O/n2.out" 2> "$O/n2.err" \
+  timeout -k 10 700 python -u bench.py --full --gpus 2 --backend gloo --steps 5 --warmup 2 > "$O/n2.out" 2> "$O/n2.err" \
     || { echo N2_FAIL; tail -30 "$O/n2.err"; exit 24; }
   grep '^{' "$O/n2.out" | tail -1 > "$O/bench_n2.json"; python3 tools/bench_summary.py "$O/bench_n2.json"
 fi
