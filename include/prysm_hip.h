@@ -94,6 +94,12 @@ uint64_t pz_set_small_batch_threshold(uint64_t compressions);
  * readable bytes past msgs[offsets[n]-1] (the library's own buffers are padded). */
 int pz_dev_blake2b512_batch(const uint8_t* d_msgs, const uint64_t* d_offsets, uint64_t n,
                             uint8_t* d_out, uint32_t out_bytes, void* stream);
+/* Messages where they lie: message i is d_msgs[d_begs[i] .. d_ends[i]); spans may overlap or
+ * leave gaps (the CSR form is d_offsets, d_offsets + 1), with the same 4 readable bytes past
+ * the last one.  Over pz_block_cols_out's att_beg / att_end this is types/attestation.go:55-58
+ * (*Attestation).Hash of every attestation of a batch of received blocks, in one launch. */
+int pz_dev_blake2b512_spans(const uint8_t* d_msgs, const uint64_t* d_begs, const uint64_t* d_ends, uint64_t n,
+                            uint8_t* d_out, uint32_t out_bytes, void* stream);
 /* Fixed-length records: message i is d_msgs[i*stride .. i*stride+len); stride % 16 == 0,
  * d_msgs 16-byte aligned, stride >= len.  This is the batched-record fast path.  The kernels
  * load whole aligned chunks, so the buffer must be readable up to the end of the last
@@ -171,6 +177,95 @@ int pz_wire_attestations(const pz_attestation_cols* a, uint64_t n, uint32_t fiel
  * d_offsets n+1 entries (required). */
 int pz_dev_wire_attestations(const pz_attestation_cols* a, uint64_t n, uint32_t field_num, uint8_t* d_out,
                              uint64_t* d_offsets, void* d_scratch, void* stream);
+
+/* ---- §8f: proto3 decoding of AttestationRecords on the device -------------------------
+ * The inverse of pz_wire_attestations.  Replaces golang/protobuf proto.Unmarshal of the
+ * AttestationRecords (messages.pb.go:889-896) of a received BeaconBlock (sync/service.go:147-164)
+ * and of a stored ActiveState (types/state.go:141's inverse), under the engine's rule that an
+ * input is accepted only if it is the canonical encoding of its own decoding (types/block.go:69
+ * hashes Marshal of the DECODED message): minimal varints for keys, values and lengths (a
+ * 10-byte varint ends in 0x01, nothing is longer), fields 1-8 with their wire types only,
+ * ascending, only field 7 repeating and only in a run, zero scalars and empty singular bytes
+ * absent, empty field-7 elements allowed, field 8 packed, non-empty, every varint in it whole
+ * and minimal, no length reaching past the record.
+ * Record i is bytes[begs[i] .. ends[i]) (a CSR batch passes offsets and offsets + 1).
+ * field_num == 0: a bare record; field_num > 0: the span starts with that field's key and a
+ * minimal length that covers exactly the rest of the span (what pz_wire_attestations emits).
+ * A record that fails gets status[i] = PZ_EINVAL, scalars 0 and empty ranges in every offsets
+ * column, so the other records' columns are what they would be without it; the call returns
+ * PZ_OK.  totals[7]: justified_block_hash bytes, shard_block_hash bytes, bitfield bytes,
+ * elements, element bytes, sig values, bad records.
+ * Output bounds, with B the batch's byte count (the sum of the spans): every bytes column
+ * (the elements' included) holds B bytes, oblique_offs B/2 + 1 entries (an element takes two
+ * bytes at least), aggregate_sig B values (a value takes one), every other offsets column n+1.
+ * The kernels read no byte outside the spans (the contract allows up to 16 bytes after the last
+ * byte of the buffer, as the hash kernels' pad; this form reads none) and write only inside the
+ * ranges their scans assign. */
+typedef struct pz_attestation_cols_out {
+  uint64_t* slot;                          /* n */
+  uint64_t* shard_id;
+  uint64_t* justified_slot;
+  uint8_t*  justified_block_hash;
+  uint64_t* justified_block_hash_offs;     /* n+1 */
+  uint8_t*  shard_block_hash;
+  uint64_t* shard_block_hash_offs;
+  uint8_t*  attester_bitfield;
+  uint64_t* attester_bitfield_offs;
+  uint8_t*  oblique_parent_hashes;
+  uint64_t* oblique_offs;                  /* m+1, m = oblique_first[n] */
+  uint64_t* oblique_first;                 /* n+1 */
+  uint64_t* aggregate_sig;
+  uint64_t* aggregate_sig_first;           /* n+1 */
+  uint64_t* n_oblique;                     /* optional, n: pz_att_check_batch.n_oblique */
+  uint8_t*  last_byte;                     /* optional, n: pz_att_check_batch.last_byte (0 when the
+                                              bitfield is empty) */
+  int32_t*  status;                        /* n: PZ_OK, or PZ_EINVAL for a record that is not canonical */
+} pz_attestation_cols_out;
+uint64_t pz_unwire_attestations_scratch_bytes(uint64_t n);
+/* Device pointers, caller's stream; d_totals (device) receives the seven totals. */
+int pz_dev_unwire_attestations(const uint8_t* d_bytes, const uint64_t* d_begs, const uint64_t* d_ends,
+                               uint64_t n, uint32_t field_num, const pz_attestation_cols_out* out,
+                               uint64_t* d_totals, void* d_scratch, void* stream);
+/* Host pointers, synchronous; offsets[n+1].  caps: the capacities of justified_block_hash,
+ * shard_block_hash, attester_bitfield (bytes), oblique_offs (elements; it holds one entry
+ * more), oblique_parent_hashes (bytes) and aggregate_sig (values).  PZ_ERANGE, nothing
+ * written, when a total exceeds its capacity; totals is filled either way. */
+int pz_unwire_attestations(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint32_t field_num,
+                           const pz_attestation_cols_out* out, const uint64_t caps[6], uint64_t totals[7]);
+
+/* ---- §8f: the top level of serialized BeaconBlocks on the device ------------------------
+ * Replaces proto.Unmarshal(BeaconBlock) at sync/service.go:147-164 (messages.pb.go:224-232)
+ * down to the attestations' spans, which pz_dev_unwire_attestations decodes where they lie
+ * (field_num 0 over att_beg / att_end).  Block i is blocks[offsets[i] .. offsets[i+1]).  The
+ * rules are the ones above for fields 1-8 of the block (1, 3-6 bytes, 2 varint, 7 Timestamp,
+ * 8 repeated records) and for the Timestamp (seconds 1, nanos 2: an int32, so its varint is
+ * the sign extension of its low 32 bits); a bytes field of 4 GiB or more does not fit
+ * bytes_len and fails too.  A block that fails has status PZ_EINVAL, zero fields and no
+ * attestations.  The records' bodies are not judged here: a block is acceptable to the engine
+ * when its status and every one of its attestations' statuses are PZ_OK.
+ * Attestation rows past att_cap are not written; *natt receives their true number. */
+typedef struct pz_block_cols_out {
+  uint64_t* slot_number;                   /* n */
+  int64_t*  ts_seconds;                    /* n */
+  int64_t*  ts_nanos;                      /* n */
+  uint8_t*  has_timestamp;                 /* n: field 7 present (it may be present and empty) */
+  uint64_t* bytes_beg;                     /* n*5: fields 1, 3, 4, 5, 6 of block i at [5i .. 5i+5) */
+  uint32_t* bytes_len;                     /* n*5: spans into blocks (len 0 = absent) */
+  uint64_t* att_first;                     /* n+1: block i's attestations are rows att_first[i] .. [i+1] */
+  uint64_t* att_beg;                       /* per attestation: its bare record inside blocks */
+  uint64_t* att_end;
+  uint64_t* att_block_slot;                /* per attestation: pz_att_check_batch.block_slot */
+  uint32_t* att_block;                     /* per attestation: its block's index */
+  int32_t*  status;                        /* n: PZ_OK / PZ_EINVAL */
+} pz_block_cols_out;
+uint64_t pz_unwire_blocks_scratch_bytes(uint64_t n);
+/* Device pointers, caller's stream; *d_natt (device) receives the number of attestations. */
+int pz_dev_unwire_blocks(const uint8_t* d_blocks, const uint64_t* d_offsets, uint64_t n, uint64_t att_cap,
+                         const pz_block_cols_out* out, uint64_t* d_natt, void* d_scratch, void* stream);
+/* Host pointers, synchronous, same results.  PZ_ERANGE (nothing written, *natt filled) when
+ * att_cap is short. */
+int pz_unwire_blocks(const uint8_t* blocks, const uint64_t* offsets, uint64_t n, uint64_t att_cap,
+                     const pz_block_cols_out* out, uint64_t* natt);
 
 /* ---- T/R: validator-set filters (casper/validator.go) ------------------------------- */
 #define PZ_KIND_ACTIVE 0  /* start <= dyn < end        casper/validator.go:45-53 */

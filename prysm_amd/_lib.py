@@ -62,6 +62,7 @@ SIGNATURES = {
     "pz_chain_set_options": [vp, vp],
     "pz_set_small_batch_threshold": [u64],
     "pz_dev_blake2b512_batch": [vp, vp, u64, vp, u32, vp],
+    "pz_dev_blake2b512_spans": [vp, vp, vp, u64, vp, u32, vp],
     "pz_dev_blake2b512_fixed": [vp, u64, u64, u64, vp, u32, vp],
     "pz_validator_indices": [vp, vp, u64, u64, ctypes.c_int, vp, c_u64p],
     "pz_attesters_total_deposit": [vp, u64, c_u64p],
@@ -96,6 +97,12 @@ SIGNATURES = {
     "pz_wire_attestations_scratch_bytes": [u64],
     "pz_wire_attestations": [vp, u64, u32, vp, u64, vp, c_u64p],
     "pz_dev_wire_attestations": [vp, u64, u32, vp, vp, vp, vp],
+    "pz_unwire_attestations_scratch_bytes": [u64],
+    "pz_dev_unwire_attestations": [vp, vp, vp, u64, u32, vp, vp, vp, vp],
+    "pz_unwire_attestations": [vp, vp, u64, u32, vp, vp, vp],
+    "pz_unwire_blocks_scratch_bytes": [u64],
+    "pz_dev_unwire_blocks": [vp, vp, u64, u64, vp, vp, vp, vp],
+    "pz_unwire_blocks": [vp, vp, u64, u64, vp, c_u64p],
     "pz_dev_check_attestations": [vp, vp],
     "pz_shutdown": [],
     "pz_state_new": [u64, ctypes.c_int, vp],
@@ -198,6 +205,20 @@ class AttestationCols(ctypes.Structure):
     ]
 
 
+class AttestationColsOut(ctypes.Structure):
+    """Mirror of ``pz_attestation_cols_out`` (include/prysm_hip.h)."""
+    _fields_ = AttestationCols._fields_ + [("n_oblique", vp), ("last_byte", vp), ("status", vp)]
+
+
+class BlockColsOut(ctypes.Structure):
+    """Mirror of ``pz_block_cols_out`` (include/prysm_hip.h)."""
+    _fields_ = [
+        ("slot_number", vp), ("ts_seconds", vp), ("ts_nanos", vp), ("has_timestamp", vp), ("bytes_beg", vp),
+        ("bytes_len", vp), ("att_first", vp), ("att_beg", vp), ("att_end", vp), ("att_block_slot", vp),
+        ("att_block", vp), ("status", vp),
+    ]
+
+
 class AttCheckBatch(ctypes.Structure):
     """Mirror of ``pz_att_check_batch`` (include/prysm_hip.h)."""
     _fields_ = [
@@ -215,7 +236,8 @@ KIND_ACTIVE, KIND_EXITED, KIND_QUEUED = 0, 1, 2
 _RESTYPES = {"pz_last_error": ctypes.c_char_p, "pz_chain_free": None, "pz_set_serial_threshold": u64, "pz_set_host_threads": u32,
              "pz_shutdown": None, "pz_state_free": None, "pz_set_small_batch_threshold": u64, "pz_comm_free": None, "pz_epoch_state_free": None,
              "pz_wire_validators_bound": u64, "pz_wire_scratch_bytes": u64,
-             "pz_wire_attestations_bound": u64, "pz_wire_attestations_scratch_bytes": u64}
+             "pz_wire_attestations_bound": u64, "pz_wire_attestations_scratch_bytes": u64,
+             "pz_unwire_attestations_scratch_bytes": u64, "pz_unwire_blocks_scratch_bytes": u64}
 SERIAL_DEFAULT = 65536        # the library's default serial threshold (bytes)
 SERIAL_ON_GPU = (1 << 64) - 1  # pz_set_serial_threshold value that keeps every message on the GPU
 

@@ -21,6 +21,7 @@ heavy work, batched per call:
 Where the reference panics, ``ChainPanic`` is raised and the chain object is spent.
 """
 import ctypes
+import warnings
 
 import numpy as np
 
@@ -35,6 +36,20 @@ BLOCK_STATUS = {0: "processed", 1: "no_parent", 2: "attestations_rejected", 3: "
 ATT_PROCESSED, ATT_NOT_PROCESSED = 0, 1
 ATT_ERRORS = {2: "slot too high", 3: "slot too low", 4: "justified slot mismatch", 5: "no committee",
               6: "bitfield length", 7: "non-zero trailing bits"}
+
+
+def _committee_table(shard_and_committees):
+    """ShardAndCommitteesForSlots (a list per slot of ``(shard_id, committee)`` pairs) as the
+    pz_att_check_batch table: arr_offs, arr_shard, arr_comm, coffs."""
+    u64 = np.uint64
+    arr_offs = np.zeros(len(shard_and_committees) + 1, dtype=u64)
+    arr_offs[1:] = np.cumsum([len(arr) for arr in shard_and_committees], dtype=u64)
+    entries = [e for arr in shard_and_committees for e in arr]
+    arr_shard = np.ascontiguousarray([e[0] for e in entries] or [0], dtype=u64)
+    arr_comm = np.arange(max(len(entries), 1), dtype=np.uint32)
+    coffs = np.zeros(len(entries) + 1, dtype=u64)
+    coffs[1:] = np.cumsum([len(e[1]) for e in entries], dtype=u64)
+    return arr_offs, arr_shard, arr_comm, coffs
 
 
 def check_attestations(atts, block_slots, last_justified_slot, last_state_recalc, n_recent,
@@ -59,13 +74,7 @@ def check_attestations(atts, block_slots, last_justified_slot, last_state_recalc
     boffs = np.zeros(n + 1, dtype=u64)
     boffs[1:] = np.cumsum([len(x) for x in bf], dtype=u64)
     bits = np.frombuffer(b"".join(bf) + b"\0", dtype=np.uint8)
-    arr_offs = np.zeros(len(shard_and_committees) + 1, dtype=u64)
-    arr_offs[1:] = np.cumsum([len(arr) for arr in shard_and_committees], dtype=u64)
-    entries = [e for arr in shard_and_committees for e in arr]
-    arr_shard = np.ascontiguousarray([e[0] for e in entries] or [0], dtype=u64)
-    arr_comm = np.arange(max(len(entries), 1), dtype=np.uint32)
-    coffs = np.zeros(len(entries) + 1, dtype=u64)
-    coffs[1:] = np.cumsum([len(e[1]) for e in entries], dtype=u64)
+    arr_offs, arr_shard, arr_comm, coffs = _committee_table(shard_and_committees)
     status = np.zeros(max(n, 1), dtype=np.int32)
     comm = np.zeros(max(n, 1), dtype=np.uint32)
     pstart = np.zeros(max(n, 1), dtype=u64)
@@ -78,6 +87,57 @@ def check_attestations(atts, block_slots, last_justified_slot, last_state_recalc
     ci = comm[:n].astype(np.int64)
     ci[comm[:n] == 0xFFFFFFFF] = -1
     return status[:n], ci, pstart[:n]
+
+
+def check_serialized_blocks(data, offsets, last_justified_slot, last_state_recalc, n_recent, shard_and_committees,
+                            device=0):
+    """:func:`check_attestations` for a batch of received blocks held as bytes (block i is
+    ``data[offsets[i]:offsets[i+1]]``, as the sync service receives them, sync/service.go:147-164):
+    the bytes go to the device once and are split (``pz_dev_unwire_blocks``), decoded
+    (``pz_dev_unwire_attestations`` over the attestations' spans) and checked
+    (``pz_dev_check_attestations``) there, on the current stream; no column visits the host in
+    between (only the attestation count does, to size the launches).
+
+    Returns ``(block_status, att_first, att_status, committee_index, parents_start)``:
+    block_status[i] is PZ_OK, or PZ_EINVAL where the engine rejects the block's bytes (its top
+    level or one of its attestations is not canonical); block i's attestations are rows
+    att_first[i] .. att_first[i+1] of the other three, which are what check_attestations returns,
+    except that an attestation whose record is not canonical reports PZ_EINVAL."""
+    import torch
+
+    dev = torch.device("cuda", device)
+    data = np.ascontiguousarray(_lib.as_u8(data), dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+
+    def up(a):
+        a = a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32) if a.dtype == np.uint32 else a
+        with warnings.catch_warnings():  # (a read-only source, e.g. np.frombuffer: it is only copied from)
+            warnings.simplefilter("ignore", UserWarning)
+            return torch.from_numpy(a).to(dev)
+
+    d_bytes, d_offs = up(data if data.size else np.zeros(1, np.uint8)), up(offsets)
+    blk = wire.unwire_blocks_device(d_bytes, d_offs, n)
+    natt = int(blk["natt"].item())
+    att = wire.unwire_attestations_device(d_bytes, blk["att_beg"], blk["att_end"], natt, 0)
+    table = [up(a) for a in _committee_table(shard_and_committees)]
+    status = torch.zeros(max(natt, 1), dtype=torch.int32, device=dev)
+    comm = torch.zeros(max(natt, 1), dtype=torch.int32, device=dev)
+    pstart = torch.zeros(max(natt, 1), dtype=torch.int64, device=dev)
+    b = _lib.AttCheckBatch(
+        natt, att["slot"].data_ptr(), att["justified_slot"].data_ptr(), att["shard_id"].data_ptr(),
+        att["n_oblique"].data_ptr(), att["attester_bitfield"].data_ptr(), att["attester_bitfield_offs"].data_ptr(),
+        blk["att_block_slot"].data_ptr(), last_justified_slot, last_state_recalc, n_recent,
+        len(shard_and_committees), *[t.data_ptr() for t in table], status.data_ptr(), comm.data_ptr(),
+        pstart.data_ptr(), att["last_byte"].data_ptr())
+    lib.call("pz_dev_check_attestations", ctypes.byref(b), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    rec = att["status"][:natt]
+    status = torch.where(rec != 0, rec, status[:natt])
+    block_status = wire.folded_block_status(blk["status"], blk["att_block"][:natt], rec)
+    ci = comm[:natt].cpu().numpy().view(np.uint32).astype(np.int64)
+    ci[ci == 0xFFFFFFFF] = -1
+    return (block_status.cpu().numpy(), blk["att_first"].cpu().numpy().view(np.uint64), status.cpu().numpy(), ci,
+            pstart[:natt].cpu().numpy().view(np.uint64))
 
 
 class ChainPanic(RuntimeError):

@@ -188,6 +188,16 @@ int pz_dev_blake2b512_batch(const uint8_t* d_msgs, const uint64_t* d_offsets, ui
   return e == hipSuccess ? PZ_OK : hip_fail(e, "pz_b2b_csr_kernel");
 }
 
+int pz_dev_blake2b512_spans(const uint8_t* d_msgs, const uint64_t* d_begs, const uint64_t* d_ends, uint64_t n,
+                            uint8_t* d_out, uint32_t out_bytes, void* stream) {
+  if (out_bytes != 32 && out_bytes != 64) return fail(PZ_EINVAL, "out_bytes must be 32 or 64");
+  if (n == 0) return PZ_OK;
+  if (!d_msgs || !d_begs || !d_ends || !d_out) return fail(PZ_EINVAL, "null pointer");
+  if (reinterpret_cast<uintptr_t>(d_out) & 15) return fail(PZ_EINVAL, "d_out must be 16-B aligned");
+  hipError_t e = launch_b2b_spans(d_msgs, d_begs, d_ends, n, d_out, out_bytes, (hipStream_t)stream);
+  return e == hipSuccess ? PZ_OK : hip_fail(e, "pz_b2b_csr_kernel");
+}
+
 }  // extern "C"
 
 namespace pz {

@@ -1,0 +1,757 @@
+// proto3 decoding of AttestationRecords and BeaconBlocks on the device: the inverse of
+// wire_att.hip.
+//
+// Replaces golang/protobuf `proto.Unmarshal` at sync/service.go:147-164 (the received block,
+// messages.pb.go:224-232) with the records inside it (messages.pb.go:889-896), under the
+// engine's canonical-form rule (chain.hip parse_att / parse_block): an input is accepted only
+// if it is the encoding of its own decoding -- minimal varints, ascending fields (a repeated
+// field only repeats in a run), zero scalars and empty singular bytes absent, a packed field
+// never empty, no unknown fields.  A record that fails gets PZ_EINVAL and contributes nothing.
+//
+// Each decode is three launches, one lane per record, 256 records per workgroup (a tile):
+//   size   walks the record, applies every rule, writes the fixed-size columns (scalars, status,
+//          n_oblique, last_byte), the record's variable sizes and the tile's sums;
+//   scan   one workgroup turns the tiles' sums into the tiles' bases (and the totals);
+//   write  scans the tile's sizes again in the workgroup, adds the tile's base -- these are the
+//          offsets columns, written once -- walks the record a second time and copies.
+// No workgroup waits for another inside a launch (the encoder's size kernel orders its tiles by
+// ticket and looks back; here the order between tiles is the order between launches), and the
+// second walk reads the bytes the first one judged, so it stays inside the record.
+//
+// Reads: only bytes of [begs[i], ends[i]).  Lengths are tested as `len > end - p`, so a
+// hostile length of 2^63 never wraps.  Writes: only inside the ranges the scans assign.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <vector>
+
+#include "runtime.h"
+
+namespace pz {
+namespace {
+
+constexpr int kTile = 256, kTileWaves = kTile / 64;
+constexpr int kScanThreads = 1024;
+constexpr int kAttCols = 7;  // d_totals' order: three bytes fields, elements, element bytes, sig values, bad records
+
+typedef __attribute__((address_space(1))) uint8_t gbyte;
+
+// A reader over d[p, e): chain.hip's Reader on offsets (no pointer is formed past the record).
+// Bytes come from a 16-byte window held in registers, loaded (unaligned) at min(pos, re - 16)
+// inside the record d[rb, re): a key with its length or value is one load, where a load per
+// varint byte was a dependent round trip each.  A record under 16 bytes, and WIN false (the A/B
+// library only), read byte by byte.
+template <bool WIN>
+struct Cur {
+  const uint8_t* d;
+  uint64_t p, e;
+  bool ok;
+  uint64_t rb, re;  // the record: what may be read
+  uint64_t w;       // the window holds d[w, w + 16) (w = re: nothing yet)
+  uint64_t lo, hi;
+};
+
+template <bool WIN>
+__device__ __forceinline__ Cur<WIN> cur_over(const uint8_t* d, uint64_t beg, uint64_t end) {
+  return Cur<WIN>{d, beg, end, true, beg, end, end, 0, 0};
+}
+
+// A reader over d[q, q + len) inside c's record; it starts with c's window.
+template <bool WIN>
+__device__ __forceinline__ Cur<WIN> cur_inside(const Cur<WIN>& c, uint64_t q, uint64_t len) {
+  Cur<WIN> s = c;
+  s.p = q;
+  s.e = q + len;
+  s.ok = true;
+  return s;
+}
+
+// The byte at pos, rb <= pos < re.
+template <bool WIN>
+__device__ __forceinline__ uint32_t byte_at(Cur<WIN>& c, uint64_t pos) {
+  if (!WIN || c.re - c.rb < 16) return c.d[pos];
+  if (pos - c.w >= 16) {  // (unsigned: a window after pos, or none yet, is far away too)
+    c.w = pos < c.re - 16 ? pos : c.re - 16;
+    uint2 v[2];
+    __builtin_memcpy(v, reinterpret_cast<const gbyte*>((uintptr_t)c.d) + c.w, 16);
+    c.lo = ((uint64_t)v[0].y << 32) | v[0].x;
+    c.hi = ((uint64_t)v[1].y << 32) | v[1].x;
+  }
+  const uint32_t off = (uint32_t)(pos - c.w);
+  return (uint32_t)((off < 8 ? c.lo >> (8 * off) : c.hi >> (8 * (off - 8))) & 0xff);
+}
+
+// a minimal varint (a 10-byte one must end in 0x01: only bit 63 left)
+template <bool WIN>
+__device__ __forceinline__ uint64_t get_varint(Cur<WIN>& c) {
+  uint64_t x = 0;
+  for (int i = 0, s = 0; i < 10; ++i, s += 7) {
+    if (c.p >= c.e) break;
+    const uint32_t b = byte_at(c, c.p++);
+    x |= (uint64_t)(b & 0x7f) << s;
+    if (!(b & 0x80)) {
+      if ((i > 0 && b == 0) || (i == 9 && b != 1)) c.ok = false;
+      return x;
+    }
+  }
+  c.ok = false;
+  return 0;
+}
+
+// a length and the bytes it covers: *q receives their start
+template <bool WIN>
+__device__ __forceinline__ uint64_t get_span(Cur<WIN>& c, uint64_t* q) {
+  const uint64_t len = get_varint(c);
+  if (!c.ok || len > c.e - c.p) {
+    c.ok = false;
+    return 0;
+  }
+  *q = c.p;
+  c.p += len;
+  return len;
+}
+
+// 16-byte unaligned pieces, the last one overlapping the one before it with the same bytes:
+// every load and store lies inside [0, len) (gfx950 runs unaligned global accesses).  PIECES
+// false (the A/B library only): byte by byte.
+__device__ __forceinline__ void copy16(gbyte* dst, const gbyte* src) {
+  uint4 v;
+  __builtin_memcpy(&v, src, 16);
+  __builtin_memcpy(dst, &v, 16);
+}
+
+template <bool PIECES>
+__device__ __forceinline__ void copy_span(uint8_t* dst, const uint8_t* src, uint64_t len) {
+  gbyte* o = reinterpret_cast<gbyte*>((uintptr_t)dst);
+  const gbyte* s = reinterpret_cast<const gbyte*>((uintptr_t)src);
+  if (PIECES && len >= 16) {
+    uint64_t k = 0;
+    for (; k + 16 <= len; k += 16) copy16(o + k, s + k);
+    if (k < len) copy16(o + len - 16, s + len - 16);
+  } else {
+    for (uint64_t k = 0; k < len; ++k) o[k] = s[k];
+  }
+}
+
+__device__ __forceinline__ uint64_t wsum(uint64_t x) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
+  return x;
+}
+
+// Inclusive scan over the wave.
+__device__ __forceinline__ uint64_t wscan(uint64_t x) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint64_t y = __shfl_up(x, d, 64);
+    if (lane >= d) x += y;
+  }
+  return x;
+}
+
+// The tile's sums of N values per lane, to tiles[c * ntiles + blockIdx.x].
+template <int N>
+__device__ __forceinline__ void tile_sums(const uint64_t (&v)[N], uint64_t* tiles, uint64_t ntiles) {
+  __shared__ uint64_t s_sum[N][kTileWaves];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int c = 0; c < N; ++c) {
+    const uint64_t t = wsum(v[c]);
+    if (lane == 0) s_sum[c][w] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < N) {
+    uint64_t t = 0;
+    for (int k = 0; k < kTileWaves; ++k) t += s_sum[threadIdx.x][k];
+    tiles[threadIdx.x * ntiles + blockIdx.x] = t;
+  }
+}
+
+// Each lane's exclusive prefix of N values within the tile (every lane of the workgroup calls).
+template <int N>
+__device__ __forceinline__ void tile_excl(const uint64_t (&v)[N], uint64_t (&ex)[N]) {
+  __shared__ uint64_t s_inc[N][kTileWaves];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  uint64_t inc[N];
+#pragma unroll
+  for (int c = 0; c < N; ++c) {
+    inc[c] = wscan(v[c]);
+    if (lane == 63) s_inc[c][w] = inc[c];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < N; ++c) {
+    uint64_t before = 0;
+    for (int k = 0; k < kTileWaves; ++k) before += k < w ? s_inc[c][k] : 0;
+    ex[c] = before + inc[c] - v[c];
+  }
+}
+
+// Launch 2 of both decodes: column c's tile sums tiles[c * ntiles ..] become the tiles'
+// exclusive bases, totals[c] the column's sum.  One workgroup; a column is walked kScanThreads
+// tiles at a time with a carry.
+extern "C" __global__ void __launch_bounds__(kScanThreads) pz_unwire_scan_kernel(uint64_t* tiles, uint64_t ntiles,
+                                                                                 uint32_t ncols, uint64_t* totals) {
+  __shared__ uint64_t s_inc[kScanThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (uint32_t c = 0; c < ncols; ++c) {
+    uint64_t* col = tiles + c * ntiles;
+    uint64_t carry = 0;
+    for (uint64_t t0 = 0; t0 < ntiles; t0 += kScanThreads) {
+      const uint64_t t = t0 + tid;
+      const uint64_t x = t < ntiles ? col[t] : 0;
+      const uint64_t inc = wscan(x);
+      if (lane == 63) s_inc[w] = inc;
+      __syncthreads();
+      uint64_t before = 0, all = 0;
+      for (int k = 0; k < kScanThreads / 64; ++k) {
+        before += k < w ? s_inc[k] : 0;
+        all += s_inc[k];
+      }
+      __syncthreads();  // (s_inc is rewritten by the next round)
+      if (t < ntiles) col[t] = carry + before + inc - x;
+      carry += all;
+    }
+    if (tid == 0) totals[c] = carry;
+  }
+}
+
+// ---- AttestationRecord ------------------------------------------------------------------------
+struct AttArgs {
+  const uint8_t* d;
+  const uint64_t* begs;
+  const uint64_t* ends;
+  uint64_t n, ntiles;
+  uint32_t field;
+  pz_attestation_cols_out o;
+  uint64_t* sizes;  // [6][n]: columns 0-5 of d_totals' order
+  uint64_t* tiles;  // [7][ntiles]
+};
+
+struct AttRec {
+  uint64_t v[3];            // slot, shard_id, justified_slot
+  uint64_t pos[3], len[3];  // fields 4-6: where the bytes are
+  uint64_t nel, elb, nsig;  // elements, their bytes, packed values
+};
+
+// Where the second walk writes: the record's first element / element byte / sig value.
+struct AttDst {
+  uint64_t el, elb, sig;
+};
+
+// parse_att (chain.hip), to the letter: messages.pb.go:889-896, 1-3 varint, 4-6 bytes,
+// 7 repeated bytes, 8 packed varints.  W: also write the elements and the sig values.
+template <bool W, bool PIECES = true, bool WIN = true>
+__device__ __forceinline__ bool walk_att(const AttArgs& a, uint64_t beg, uint64_t end, AttRec& r, const AttDst& dst) {
+  r = AttRec{};
+  if (end < beg) return false;
+  Cur<WIN> c = cur_over<WIN>(a.d, beg, end);
+  if (a.field) {  // the frame: that field's key and a length that covers exactly the rest
+    const uint64_t k = get_varint(c);
+    if (!c.ok || k != (((uint64_t)a.field << 3) | 2)) return false;
+    const uint64_t len = get_varint(c);
+    if (!c.ok || len != c.e - c.p) return false;
+  }
+  uint64_t prev = 0;
+  while (c.p < c.e) {
+    const uint64_t k = get_varint(c);
+    const uint64_t f = k >> 3;
+    if (!c.ok || f == 0 || f > 8 || (k & 7) != (f <= 3 ? 0u : 2u)) return false;
+    if (f < prev || (f == prev && f != 7)) return false;
+    prev = f;
+    if (f <= 3) {
+      const uint64_t v = get_varint(c);
+      if (!c.ok || !v) return false;  // a zero scalar is omitted by Marshal
+#pragma unroll
+      for (int k = 0; k < 3; ++k)  // (constant indices: the record stays in registers)
+        if (f == 1u + k) r.v[k] = v;
+      continue;
+    }
+    uint64_t q = 0;
+    const uint64_t len = get_span(c, &q);
+    if (!c.ok) return false;
+    if (f <= 6) {
+      if (!len) return false;  // an empty singular bytes field is omitted
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        if (f == 4u + k) {
+          r.pos[k] = q;
+          r.len[k] = len;
+        }
+    } else if (f == 7) {  // every element is emitted, an empty one too
+      if (W) {
+        a.o.oblique_offs[dst.el + r.nel] = dst.elb + r.elb;
+        copy_span<PIECES>(a.o.oblique_parent_hashes + dst.elb + r.elb, a.d + q, len);
+      }
+      ++r.nel;
+      r.elb += len;
+    } else {  // f == 8: packed, never empty, every varint whole and minimal
+      if (!len) return false;
+      Cur<WIN> s = cur_inside(c, q, len);
+      while (s.ok && s.p < s.e) {
+        const uint64_t x = get_varint(s);
+        if (W && s.ok) a.o.aggregate_sig[dst.sig + r.nsig] = x;
+        ++r.nsig;
+      }
+      if (!s.ok) return false;
+    }
+  }
+  return true;
+}
+
+template <bool WIN>
+__device__ __forceinline__ void att_size_body(const AttArgs& a) {
+  const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+  uint64_t sz[kAttCols] = {0, 0, 0, 0, 0, 0, 0};
+  if (i < a.n) {
+    AttRec r;
+    const bool ok = walk_att<false, true, WIN>(a, a.begs[i], a.ends[i], r, AttDst{});
+    if (!ok) r = AttRec{};  // a record that fails contributes nothing
+    a.o.slot[i] = r.v[0];
+    a.o.shard_id[i] = r.v[1];
+    a.o.justified_slot[i] = r.v[2];
+    a.o.status[i] = ok ? PZ_OK : PZ_EINVAL;
+    if (a.o.n_oblique) a.o.n_oblique[i] = r.nel;
+    if (a.o.last_byte) a.o.last_byte[i] = r.len[2] ? a.d[r.pos[2] + r.len[2] - 1] : 0;
+    sz[0] = r.len[0];
+    sz[1] = r.len[1];
+    sz[2] = r.len[2];
+    sz[3] = r.nel;
+    sz[4] = r.elb;
+    sz[5] = r.nsig;
+    sz[6] = !ok;
+#pragma unroll
+    for (int c = 0; c < kAttCols - 1; ++c) a.sizes[c * a.n + i] = sz[c];
+  }
+  tile_sums<kAttCols>(sz, a.tiles, a.ntiles);
+}
+
+extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_att_size_kernel(AttArgs a) { att_size_body<true>(a); }
+
+template <bool PIECES, bool WIN = true>
+__device__ __forceinline__ void att_write_body(const AttArgs& a) {
+  const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+  uint64_t sz[kAttCols - 1], at[kAttCols - 1];
+#pragma unroll
+  for (int c = 0; c < kAttCols - 1; ++c) sz[c] = i < a.n ? a.sizes[c * a.n + i] : 0;
+  tile_excl<kAttCols - 1>(sz, at);
+  if (i >= a.n) return;
+#pragma unroll
+  for (int c = 0; c < kAttCols - 1; ++c) at[c] += a.tiles[c * a.ntiles + blockIdx.x];
+  uint64_t* const offs[kAttCols - 1] = {a.o.justified_block_hash_offs, a.o.shard_block_hash_offs,
+                                        a.o.attester_bitfield_offs,    a.o.oblique_first,
+                                        nullptr,                       a.o.aggregate_sig_first};
+#pragma unroll
+  for (int c = 0; c < kAttCols - 1; ++c) {
+    if (!offs[c]) continue;
+    offs[c][i] = at[c];
+    if (i + 1 == a.n) offs[c][a.n] = at[c] + sz[c];
+  }
+  if (i + 1 == a.n) a.o.oblique_offs[at[3] + sz[3]] = at[4] + sz[4];  // the element CSR's end
+  if (a.o.status[i] != PZ_OK) return;
+  AttRec r;
+  walk_att<true, PIECES, WIN>(a, a.begs[i], a.ends[i], r, AttDst{at[3], at[4], at[5]});
+  uint8_t* const dat[3] = {a.o.justified_block_hash, a.o.shard_block_hash, a.o.attester_bitfield};
+#pragma unroll
+  for (int k = 0; k < 3; ++k) copy_span<PIECES>(dat[k] + at[k], a.d + r.pos[k], r.len[k]);
+}
+
+extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_att_write_kernel(AttArgs a) { att_write_body<true>(a); }
+#ifdef PZ_AB_BUILD
+extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_att_write_bytes_kernel(AttArgs a) {
+  att_write_body<false>(a);
+}
+extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_att_size_loads_kernel(AttArgs a) {
+  att_size_body<false>(a);
+}
+extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_att_write_loads_kernel(AttArgs a) {
+  att_write_body<true, false>(a);
+}
+int g_unwire_variant = 0;  // 1: the write kernel's copies byte by byte; 2: both walks a load per byte
+#endif
+
+int att_out_args(const pz_attestation_cols_out* o, uint64_t n, uint32_t field_num) {
+  if (!o) return fail(PZ_EINVAL, "columns are null");
+  if (field_num >= (1u << 29)) return fail(PZ_EINVAL, "field number %u out of range", field_num);
+  if (n >> 38) return fail(PZ_EINVAL, "more than 2^38 records");  // (a tile per workgroup: the grid's limit)
+  if (!o->justified_block_hash_offs || !o->shard_block_hash_offs || !o->attester_bitfield_offs || !o->oblique_offs ||
+      !o->oblique_first || !o->aggregate_sig_first)
+    return fail(PZ_EINVAL, "null offsets column");
+  if (n && (!o->slot || !o->shard_id || !o->justified_slot || !o->justified_block_hash || !o->shard_block_hash ||
+            !o->attester_bitfield || !o->oblique_parent_hashes || !o->aggregate_sig || !o->status))
+    return fail(PZ_EINVAL, "null output column");
+  return PZ_OK;
+}
+
+uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
+uint64_t pad256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
+
+hipError_t launch_unwire_att(AttArgs a, uint64_t* totals, void* scratch, hipStream_t s) {
+  hipError_t e;
+  if (!a.n) {  // every offsets column is its first entry
+    uint64_t* const first[] = {a.o.justified_block_hash_offs, a.o.shard_block_hash_offs, a.o.attester_bitfield_offs,
+                               a.o.oblique_offs,              a.o.oblique_first,         a.o.aggregate_sig_first};
+    for (uint64_t* p : first)
+      if ((e = hipMemsetAsync(p, 0, 8, s)) != hipSuccess) return e;
+    return hipMemsetAsync(totals, 0, kAttCols * 8, s);
+  }
+  a.ntiles = tiles_of(a.n);
+  a.sizes = static_cast<uint64_t*>(scratch);
+  a.tiles = a.sizes + (kAttCols - 1) * a.n;
+#ifdef PZ_AB_BUILD
+  if (g_unwire_variant == 2)
+    hipLaunchKernelGGL(pz_unwire_att_size_loads_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
+  else
+#endif
+    hipLaunchKernelGGL(pz_unwire_att_size_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(pz_unwire_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, a.tiles, a.ntiles, (uint32_t)kAttCols,
+                     totals);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+#ifdef PZ_AB_BUILD
+  if (g_unwire_variant == 1 || g_unwire_variant == 2) {
+    hipLaunchKernelGGL(g_unwire_variant == 1 ? pz_unwire_att_write_bytes_kernel : pz_unwire_att_write_loads_kernel,
+                       dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
+    return hipGetLastError();
+  }
+#endif
+  hipLaunchKernelGGL(pz_unwire_att_write_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
+  return hipGetLastError();
+}
+
+// ---- BeaconBlock: the top level only ----------------------------------------------------------
+struct BlockArgs {
+  const uint8_t* d;
+  const uint64_t* offs;
+  uint64_t n, ntiles, att_cap;
+  pz_block_cols_out o;
+  uint64_t* counts;  // [n]
+  uint64_t* tiles;   // [ntiles]
+};
+
+struct BlockRec {
+  uint64_t slot;
+  int64_t ts_seconds, ts_nanos;
+  bool has_ts;
+  uint64_t beg[5];  // fields 1, 3, 4, 5, 6
+  uint32_t len[5];
+  uint64_t natt;
+};
+
+// parse_block's top level (chain.hip): messages.pb.go:224-232, 1 bytes, 2 varint, 3-6 bytes,
+// 7 Timestamp {int64 seconds = 1; int32 nanos = 2} (may be empty), 8 repeated records, jumped
+// over by their lengths.  W: also write the spans of the block's records, rows first + j.
+template <bool W>
+__device__ __forceinline__ bool walk_block(const BlockArgs& a, uint64_t i, uint64_t beg, uint64_t end, BlockRec& r,
+                                           uint64_t first) {
+  r = BlockRec{};
+  if (end < beg) return false;
+  Cur<true> c = cur_over<true>(a.d, beg, end);
+  uint64_t prev = 0;
+  while (c.p < c.e) {
+    const uint64_t k = get_varint(c);
+    const uint64_t f = k >> 3;
+    if (!c.ok || f == 0 || f > 8 || (k & 7) != (f == 2 ? 0u : 2u)) return false;
+    if (f < prev || (f == prev && f != 8)) return false;
+    prev = f;
+    if (f == 2) {
+      if (!(r.slot = get_varint(c)) || !c.ok) return false;
+      continue;
+    }
+    uint64_t q = 0;
+    const uint64_t len = get_span(c, &q);
+    if (!c.ok) return false;
+    if (f <= 6) {
+      if (!len || len > 0xffffffffull) return false;  // (bytes_len is 32 bits)
+#pragma unroll
+      for (int s = 0; s < 5; ++s)  // fields 1, 3, 4, 5, 6 (constant indices: no private array)
+        if (f == (s ? s + 2u : 1u)) {
+          r.beg[s] = q;
+          r.len[s] = (uint32_t)len;
+        }
+    } else if (f == 7) {
+      r.has_ts = true;
+      Cur<true> t = cur_inside(c, q, len);
+      uint64_t tp = 0;
+      while (t.p < t.e) {
+        const uint64_t tk = get_varint(t);
+        const uint64_t tf = tk >> 3;
+        if (!t.ok || tf == 0 || tf > 2 || (tk & 7) != 0 || tf <= tp) return false;
+        tp = tf;
+        const uint64_t v = get_varint(t);
+        if (!t.ok || !v) return false;
+        // int32: Marshal sign-extends the decoded 32-bit value
+        if (tf == 2 && v != (uint64_t)(int64_t)(int32_t)(uint32_t)v) return false;
+        (tf == 1 ? r.ts_seconds : r.ts_nanos) = (int64_t)v;
+      }
+    } else {  // f == 8
+      const uint64_t row = first + r.natt;
+      if (W && row < a.att_cap) {
+        a.o.att_beg[row] = q;
+        a.o.att_end[row] = q + len;
+        a.o.att_block_slot[row] = r.slot;
+        a.o.att_block[row] = (uint32_t)i;
+      }
+      ++r.natt;
+    }
+  }
+  return true;
+}
+
+extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_block_size_kernel(BlockArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+  uint64_t cnt[1] = {0};
+  if (i < a.n) {
+    BlockRec r;
+    const bool ok = walk_block<false>(a, i, a.offs[i], a.offs[i + 1], r, 0);
+    if (!ok) r = BlockRec{};  // a block that fails has no fields and no attestations
+    a.o.slot_number[i] = r.slot;
+    a.o.ts_seconds[i] = r.ts_seconds;
+    a.o.ts_nanos[i] = r.ts_nanos;
+    a.o.has_timestamp[i] = r.has_ts;
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+      a.o.bytes_beg[i * 5 + s] = r.beg[s];
+      a.o.bytes_len[i * 5 + s] = r.len[s];
+    }
+    a.o.status[i] = ok ? PZ_OK : PZ_EINVAL;
+    a.counts[i] = cnt[0] = r.natt;
+  }
+  tile_sums<1>(cnt, a.tiles, a.ntiles);
+}
+
+extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_block_write_kernel(BlockArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+  uint64_t cnt[1] = {i < a.n ? a.counts[i] : 0}, at[1];
+  tile_excl<1>(cnt, at);
+  if (i >= a.n) return;
+  const uint64_t first = at[0] + a.tiles[blockIdx.x];
+  a.o.att_first[i] = first;
+  if (i + 1 == a.n) a.o.att_first[a.n] = first + cnt[0];
+  if (!cnt[0]) return;
+  BlockRec r;
+  walk_block<true>(a, i, a.offs[i], a.offs[i + 1], r, first);
+}
+
+int block_out_args(const pz_block_cols_out* o, uint64_t n, uint64_t att_cap) {
+  if (!o) return fail(PZ_EINVAL, "columns are null");
+  if (n >> 32) return fail(PZ_EINVAL, "more than 2^32 blocks");
+  if (!o->att_first) return fail(PZ_EINVAL, "att_first is null");
+  if (n && (!o->slot_number || !o->ts_seconds || !o->ts_nanos || !o->has_timestamp || !o->bytes_beg || !o->bytes_len ||
+            !o->status))
+    return fail(PZ_EINVAL, "null output column");
+  if (att_cap && (!o->att_beg || !o->att_end || !o->att_block_slot || !o->att_block))
+    return fail(PZ_EINVAL, "null attestation column");
+  return PZ_OK;
+}
+
+hipError_t launch_unwire_blocks(BlockArgs a, uint64_t* natt, void* scratch, hipStream_t s) {
+  hipError_t e;
+  if (!a.n) {
+    if ((e = hipMemsetAsync(a.o.att_first, 0, 8, s)) != hipSuccess) return e;
+    return hipMemsetAsync(natt, 0, 8, s);
+  }
+  a.ntiles = tiles_of(a.n);
+  a.counts = static_cast<uint64_t*>(scratch);
+  a.tiles = a.counts + a.n;
+  hipLaunchKernelGGL(pz_unwire_block_size_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(pz_unwire_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, a.tiles, a.ntiles, 1u, natt);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(pz_unwire_block_write_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace
+}  // namespace pz
+
+using namespace pz;
+
+extern "C" {
+
+uint64_t pz_unwire_attestations_scratch_bytes(uint64_t n) {
+  return pad256(((kAttCols - 1) * n + kAttCols * tiles_of(n)) * 8 + 8);
+}
+
+int pz_dev_unwire_attestations(const uint8_t* d_bytes, const uint64_t* d_begs, const uint64_t* d_ends, uint64_t n,
+                               uint32_t field_num, const pz_attestation_cols_out* out, uint64_t* d_totals,
+                               void* d_scratch, void* stream) {
+  int rc = att_out_args(out, n, field_num);
+  if (rc) return rc;
+  if (!d_totals || !d_scratch || (n && (!d_bytes || !d_begs || !d_ends))) return fail(PZ_EINVAL, "null device pointer");
+  AttArgs a{};
+  a.d = d_bytes;
+  a.begs = d_begs;
+  a.ends = d_ends;
+  a.n = n;
+  a.field = field_num;
+  a.o = *out;
+  const hipError_t e = launch_unwire_att(a, d_totals, d_scratch, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? PZ_OK : hip_fail(e, "pz_unwire_att kernels");
+}
+
+int pz_unwire_attestations(const uint8_t* bytes, const uint64_t* offsets, uint64_t n, uint32_t field_num,
+                           const pz_attestation_cols_out* out, const uint64_t caps[6], uint64_t totals[7]) {
+  int rc = att_out_args(out, n, field_num);
+  if (rc) return rc;
+  if (!caps || !totals) return fail(PZ_EINVAL, "caps or totals is null");
+  if ((rc = check_csr(offsets, n, "record"))) return rc;
+  if (n && !bytes) return fail(PZ_EINVAL, "bytes is null");
+  const uint64_t nbytes = n ? offsets[n] - offsets[0] : 0;
+  DeviceCtx* ctx;
+  if ((rc = acquire(&ctx))) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if ((rc = ctx->ensure_stream())) return rc;
+  Stager st{ctx, ctx->stream};
+  const std::vector<uint64_t> rb = rebase(offsets, n);
+  AttArgs a{};
+  a.d = st.up(n ? bytes + offsets[0] : nullptr, nbytes);
+  a.begs = st.up(rb.data(), n + 1);
+  a.ends = a.begs + 1;
+  a.n = n;
+  a.field = field_num;
+  // every column at its bound: bytes columns and sig values the input's byte count, elements half
+  pz_attestation_cols_out d{};
+  d.slot = st.up<uint64_t>(nullptr, n);
+  d.shard_id = st.up<uint64_t>(nullptr, n);
+  d.justified_slot = st.up<uint64_t>(nullptr, n);
+  d.justified_block_hash = st.up<uint8_t>(nullptr, nbytes);
+  d.justified_block_hash_offs = st.up<uint64_t>(nullptr, n + 1);
+  d.shard_block_hash = st.up<uint8_t>(nullptr, nbytes);
+  d.shard_block_hash_offs = st.up<uint64_t>(nullptr, n + 1);
+  d.attester_bitfield = st.up<uint8_t>(nullptr, nbytes);
+  d.attester_bitfield_offs = st.up<uint64_t>(nullptr, n + 1);
+  d.oblique_parent_hashes = st.up<uint8_t>(nullptr, nbytes);
+  d.oblique_offs = st.up<uint64_t>(nullptr, nbytes / 2 + 1);
+  d.oblique_first = st.up<uint64_t>(nullptr, n + 1);
+  d.aggregate_sig = st.up<uint64_t>(nullptr, nbytes);
+  d.aggregate_sig_first = st.up<uint64_t>(nullptr, n + 1);
+  d.n_oblique = out->n_oblique ? st.up<uint64_t>(nullptr, n) : nullptr;
+  d.last_byte = out->last_byte ? st.up<uint8_t>(nullptr, n) : nullptr;
+  d.status = st.up<int32_t>(nullptr, n);
+  uint64_t* d_totals = st.up<uint64_t>(nullptr, kAttCols);
+  void* scratch = st.up<uint8_t>(nullptr, pz_unwire_attestations_scratch_bytes(n));
+  if (st.rc) return st.rc;
+  a.o = d;
+  st.check(launch_unwire_att(a, d_totals, scratch, st.s), "pz_unwire_att kernels");
+  st.down(totals, d_totals, kAttCols);
+  if (st.sync()) return st.rc;
+  static const char* const kWhat[6] = {"justified_block_hash", "shard_block_hash", "attester_bitfield",
+                                       "oblique elements",     "oblique bytes",    "aggregate_sig"};
+  for (int c = 0; c < 6; ++c)
+    if (totals[c] > caps[c])
+      return fail(PZ_ERANGE, "%s needs %llu, capacity %llu", kWhat[c], (unsigned long long)totals[c],
+                  (unsigned long long)caps[c]);
+  st.down(out->slot, d.slot, n);
+  st.down(out->shard_id, d.shard_id, n);
+  st.down(out->justified_slot, d.justified_slot, n);
+  st.down(out->justified_block_hash, d.justified_block_hash, totals[0]);
+  st.down(out->justified_block_hash_offs, d.justified_block_hash_offs, n + 1);
+  st.down(out->shard_block_hash, d.shard_block_hash, totals[1]);
+  st.down(out->shard_block_hash_offs, d.shard_block_hash_offs, n + 1);
+  st.down(out->attester_bitfield, d.attester_bitfield, totals[2]);
+  st.down(out->attester_bitfield_offs, d.attester_bitfield_offs, n + 1);
+  st.down(out->oblique_parent_hashes, d.oblique_parent_hashes, totals[4]);
+  st.down(out->oblique_offs, d.oblique_offs, totals[3] + 1);
+  st.down(out->oblique_first, d.oblique_first, n + 1);
+  st.down(out->aggregate_sig, d.aggregate_sig, totals[5]);
+  st.down(out->aggregate_sig_first, d.aggregate_sig_first, n + 1);
+  if (out->n_oblique) st.down(out->n_oblique, d.n_oblique, n);
+  if (out->last_byte) st.down(out->last_byte, d.last_byte, n);
+  st.down(out->status, d.status, n);
+  return st.sync();
+}
+
+uint64_t pz_unwire_blocks_scratch_bytes(uint64_t n) { return pad256((n + tiles_of(n)) * 8 + 8); }
+
+int pz_dev_unwire_blocks(const uint8_t* d_blocks, const uint64_t* d_offsets, uint64_t n, uint64_t att_cap,
+                         const pz_block_cols_out* out, uint64_t* d_natt, void* d_scratch, void* stream) {
+  int rc = block_out_args(out, n, att_cap);
+  if (rc) return rc;
+  if (!d_natt || !d_scratch || (n && (!d_blocks || !d_offsets))) return fail(PZ_EINVAL, "null device pointer");
+  BlockArgs a{};
+  a.d = d_blocks;
+  a.offs = d_offsets;
+  a.n = n;
+  a.att_cap = att_cap;
+  a.o = *out;
+  const hipError_t e = launch_unwire_blocks(a, d_natt, d_scratch, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? PZ_OK : hip_fail(e, "pz_unwire_block kernels");
+}
+
+int pz_unwire_blocks(const uint8_t* blocks, const uint64_t* offsets, uint64_t n, uint64_t att_cap,
+                     const pz_block_cols_out* out, uint64_t* natt) {
+  int rc = block_out_args(out, n, att_cap);
+  if (rc) return rc;
+  if (!natt) return fail(PZ_EINVAL, "natt is null");
+  *natt = 0;
+  if ((rc = check_csr(offsets, n, "block"))) return rc;
+  if (n && !blocks) return fail(PZ_EINVAL, "blocks is null");
+  const uint64_t nbytes = n ? offsets[n] - offsets[0] : 0, base = n ? offsets[0] : 0;
+  DeviceCtx* ctx;
+  if ((rc = acquire(&ctx))) return rc;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if ((rc = ctx->ensure_stream())) return rc;
+  Stager st{ctx, ctx->stream};
+  const std::vector<uint64_t> rb = rebase(offsets, n);
+  BlockArgs a{};
+  a.d = st.up(n ? blocks + base : nullptr, nbytes);
+  a.offs = st.up(rb.data(), n + 1);
+  a.n = n;
+  a.att_cap = att_cap;
+  pz_block_cols_out d{};
+  d.slot_number = st.up<uint64_t>(nullptr, n);
+  d.ts_seconds = st.up<int64_t>(nullptr, n);
+  d.ts_nanos = st.up<int64_t>(nullptr, n);
+  d.has_timestamp = st.up<uint8_t>(nullptr, n);
+  d.bytes_beg = st.up<uint64_t>(nullptr, n * 5);
+  d.bytes_len = st.up<uint32_t>(nullptr, n * 5);
+  d.att_first = st.up<uint64_t>(nullptr, n + 1);
+  d.att_beg = st.up<uint64_t>(nullptr, att_cap);
+  d.att_end = st.up<uint64_t>(nullptr, att_cap);
+  d.att_block_slot = st.up<uint64_t>(nullptr, att_cap);
+  d.att_block = st.up<uint32_t>(nullptr, att_cap);
+  d.status = st.up<int32_t>(nullptr, n);
+  uint64_t* d_natt = st.up<uint64_t>(nullptr, 1);
+  void* scratch = st.up<uint8_t>(nullptr, pz_unwire_blocks_scratch_bytes(n));
+  if (st.rc) return st.rc;
+  a.o = d;
+  st.check(launch_unwire_blocks(a, d_natt, scratch, st.s), "pz_unwire_block kernels");
+  st.down(natt, d_natt, 1);
+  if (st.sync()) return st.rc;
+  if (*natt > att_cap)
+    return fail(PZ_ERANGE, "%llu attestations, capacity %llu", (unsigned long long)*natt, (unsigned long long)att_cap);
+  st.down(out->slot_number, d.slot_number, n);
+  st.down(out->ts_seconds, d.ts_seconds, n);
+  st.down(out->ts_nanos, d.ts_nanos, n);
+  st.down(out->has_timestamp, d.has_timestamp, n);
+  st.down(out->bytes_beg, d.bytes_beg, n * 5);
+  st.down(out->bytes_len, d.bytes_len, n * 5);
+  st.down(out->att_first, d.att_first, n + 1);
+  st.down(out->att_beg, d.att_beg, *natt);
+  st.down(out->att_end, d.att_end, *natt);
+  st.down(out->att_block_slot, d.att_block_slot, *natt);
+  st.down(out->att_block, d.att_block, *natt);
+  st.down(out->status, d.status, n);
+  if (st.sync()) return st.rc;
+  // the spans are positions in the caller's buffer
+  for (uint64_t k = 0; base && k < n * 5; ++k)
+    if (out->bytes_len[k]) out->bytes_beg[k] += base;
+  for (uint64_t k = 0; base && k < *natt; ++k) {
+    out->att_beg[k] += base;
+    out->att_end[k] += base;
+  }
+  return PZ_OK;
+}
+
+}  // extern "C"
+
+#ifdef PZ_AB_BUILD
+extern "C" int pz_debug_set_unwire_variant(int v) {
+  const int old = pz::g_unwire_variant;
+  pz::g_unwire_variant = v;
+  return old;
+}
+#endif

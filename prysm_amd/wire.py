@@ -253,3 +253,159 @@ def attestations_device(cols, n, field_num=0):
     _lib.lib.call("pz_wire_attestations", _lib.ctypes.byref(c), n, field_num, _lib.ptr(out), cap, _lib.ptr(offs),
                   _lib.ctypes.byref(length))
     return out[:length.value].tobytes(), offs
+
+
+# ---- device decoder (prysm_amd/csrc/unwire.hip) ----------------------------------------------
+ATT_OUT_COLS = ATT_COLS + ("n_oblique", "last_byte", "status")
+BLOCK_COLS = ("slot_number", "ts_seconds", "ts_nanos", "has_timestamp", "bytes_beg", "bytes_len", "att_first",
+              "att_beg", "att_end", "att_block_slot", "att_block", "status")
+_BYTES_COLS = ("justified_block_hash", "shard_block_hash", "attester_bitfield", "oblique_parent_hashes")
+_ATT_DTYPES = {"last_byte": np.uint8, "status": np.int32}
+_BLOCK_DTYPES = {"ts_seconds": np.int64, "ts_nanos": np.int64, "has_timestamp": np.uint8, "bytes_len": np.uint32,
+                 "att_block": np.uint32, "status": np.int32}
+
+
+def _att_out_sizes(n, nbytes):
+    """Entries of every pz_attestation_cols_out column at its bound (include/prysm_hip.h)."""
+    size = {k: n for k in ATT_OUT_COLS}
+    size.update({k: nbytes for k in _BYTES_COLS})
+    size.update({k: n + 1 for k in ATT_COLS if k.endswith("_offs") or k.endswith("_first")})
+    size.update(oblique_offs=nbytes // 2 + 1, aggregate_sig=nbytes)
+    return size
+
+
+def _att_trim(cols, n, totals):
+    """Views of the bound-sized columns at their decoded lengths (``totals`` on the host)."""
+    jb, sb, bf, ne, eb, ns = (int(x) for x in totals[:6])
+    used = dict(justified_block_hash=jb, shard_block_hash=sb, attester_bitfield=bf, oblique_parent_hashes=eb,
+                oblique_offs=ne + 1, aggregate_sig=ns)
+    return {k: v[:used[k]] if k in used else v for k, v in cols.items()}
+
+
+def unwire_attestations(data, offsets, field_num=0):
+    """The inverse of :func:`attestations_device`: record i is ``data[offsets[i]:offsets[i+1]]``
+    (bare, or framed as field ``field_num``), decoded on the GPU by ``pz_unwire_attestations``.
+    Returns the columns of ``ATT_COLS`` plus ``n_oblique``, ``last_byte``, ``status`` (PZ_OK, or
+    PZ_EINVAL for a record that is not the canonical encoding of its decoding: such a record
+    has zero scalars and empty ranges) and ``totals`` (the seven totals of the header)."""
+    from prysm_amd import _lib
+
+    data = np.ascontiguousarray(_lib.as_u8(data), dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=_U64)
+    n = len(offsets) - 1
+    nbytes = int(offsets[-1] - offsets[0])
+    size = _att_out_sizes(n, nbytes)
+    cols = {k: np.zeros(max(size[k], 1), dtype=_ATT_DTYPES.get(k, np.uint8 if k in _BYTES_COLS else _U64))
+            for k in ATT_OUT_COLS}
+    c = _lib.AttestationColsOut(*[cols[k].ctypes.data for k in ATT_OUT_COLS])
+    caps = np.array([nbytes, nbytes, nbytes, nbytes // 2, nbytes, nbytes], dtype=_U64)
+    totals = np.zeros(7, dtype=_U64)
+    _lib.lib.call("pz_unwire_attestations", data.ctypes.data, offsets.ctypes.data, n, field_num,
+                  _lib.ctypes.byref(c), caps.ctypes.data, totals.ctypes.data)
+    out = _att_trim({k: v[:size[k]] for k, v in cols.items()}, n, totals)
+    out["totals"] = totals
+    return out
+
+
+def unwire_blocks(data, offsets):
+    """The top level of serialized BeaconBlocks (block i is ``data[offsets[i]:offsets[i+1]]``),
+    split on the GPU by ``pz_unwire_blocks``: the columns of ``BLOCK_COLS`` (``bytes_beg`` /
+    ``bytes_len`` as (n, 5): fields 1, 3, 4, 5, 6) with the span of every attestation.  A
+    block's ``status`` covers its top level only; :func:`folded_block_status` adds the verdicts
+    of its attestations' bodies."""
+    from prysm_amd import _lib
+
+    data = np.ascontiguousarray(_lib.as_u8(data), dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=_U64)
+    n = len(offsets) - 1
+    cap = int(offsets[-1] - offsets[0]) // 2  # a framed record takes two bytes at least
+    size = {k: n for k in BLOCK_COLS}
+    size.update(bytes_beg=5 * n, bytes_len=5 * n, att_first=n + 1, att_beg=cap, att_end=cap, att_block_slot=cap,
+                att_block=cap)
+    cols = {k: np.zeros(max(size[k], 1), dtype=_BLOCK_DTYPES.get(k, _U64)) for k in BLOCK_COLS}
+    c = _lib.BlockColsOut(*[cols[k].ctypes.data for k in BLOCK_COLS])
+    natt = _lib.ctypes.c_uint64(0)
+    _lib.lib.call("pz_unwire_blocks", data.ctypes.data, offsets.ctypes.data, n, cap, _lib.ctypes.byref(c),
+                  _lib.ctypes.byref(natt))
+    out = {k: v[:natt.value if k in ("att_beg", "att_end", "att_block_slot", "att_block") else size[k]]
+           for k, v in cols.items()}
+    out["bytes_beg"] = out["bytes_beg"].reshape(n, 5)
+    out["bytes_len"] = out["bytes_len"].reshape(n, 5)
+    out["natt"] = natt.value
+    return out
+
+
+def folded_block_status(block_status, att_block, att_status):
+    """The engine's verdict on each block: bad (PZ_EINVAL) if its top level is bad or any of its
+    attestations' records is.  numpy arrays or torch tensors (then nothing leaves the device)."""
+    from prysm_amd import _lib
+
+    bad = att_block[att_status != 0]
+    if hasattr(block_status, "clone"):
+        out = block_status.clone()
+        out[bad.long()] = _lib.PZ_EINVAL
+    else:
+        out = block_status.copy()
+        out[bad.astype(np.int64)] = _lib.PZ_EINVAL
+    return out
+
+
+def _torch_empty(torch, dev, count, np_dtype):
+    """torch has no unsigned 32/64-bit arithmetic: those columns travel as int32 / int64."""
+    dt = {np.uint8: torch.uint8, np.int32: torch.int32, np.uint32: torch.int32, np.int64: torch.int64,
+          _U64: torch.int64}[np_dtype]
+    return torch.empty(max(count, 1), dtype=dt, device=dev)
+
+
+def unwire_attestations_device(d_bytes, d_begs, d_ends, n, field_num=0, nbytes=None):
+    """``pz_dev_unwire_attestations`` on torch tensors, on the current stream: record i is
+    ``d_bytes[d_begs[i]:d_ends[i]]`` (int64 tensors; a CSR batch passes ``offs[:-1]`` and
+    ``offs[1:]``).  ``nbytes`` bounds the sum of the spans (default: all of ``d_bytes``, right
+    for spans that do not overlap).  Returns the columns of ``ATT_OUT_COLS`` as tensors at their
+    bounds and ``totals`` (7, on the device); :func:`_att_trim` cuts them once the totals are
+    on the host."""
+    import torch
+
+    from prysm_amd import _lib
+
+    dev = d_bytes.device
+    nbytes = int(d_bytes.numel()) if nbytes is None else int(nbytes)
+    size = _att_out_sizes(n, nbytes)
+    cols = {k: _torch_empty(torch, dev, size[k], _ATT_DTYPES.get(k, np.uint8 if k in _BYTES_COLS else _U64))
+            for k in ATT_OUT_COLS}
+    c = _lib.AttestationColsOut(*[cols[k].data_ptr() for k in ATT_OUT_COLS])
+    totals = torch.empty(7, dtype=torch.int64, device=dev)
+    scr = torch.empty(int(_lib.lib.dll.pz_unwire_attestations_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+    sh = _lib.ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.lib.call("pz_dev_unwire_attestations", d_bytes.data_ptr(), d_begs.data_ptr(), d_ends.data_ptr(), n,
+                  field_num, _lib.ctypes.byref(c), totals.data_ptr(), scr.data_ptr(), sh)
+    out = {k: v[:size[k]] for k, v in cols.items()}
+    out["totals"] = totals
+    return out
+
+
+def unwire_blocks_device(d_blocks, d_offsets, n, att_cap=None):
+    """``pz_dev_unwire_blocks`` on torch tensors, on the current stream.  ``att_cap`` rows are
+    allocated for the attestations (default: half the byte count, which always suffices).
+    Returns the columns of ``BLOCK_COLS`` as tensors and ``natt`` (1, on the device)."""
+    import torch
+
+    from prysm_amd import _lib
+
+    dev = d_blocks.device
+    cap = int(d_blocks.numel()) // 2 if att_cap is None else int(att_cap)
+    size = {k: n for k in BLOCK_COLS}
+    size.update(bytes_beg=5 * n, bytes_len=5 * n, att_first=n + 1, att_beg=cap, att_end=cap, att_block_slot=cap,
+                att_block=cap)
+    cols = {k: _torch_empty(torch, dev, size[k], _BLOCK_DTYPES.get(k, _U64)) for k in BLOCK_COLS}
+    c = _lib.BlockColsOut(*[cols[k].data_ptr() for k in BLOCK_COLS])
+    natt = torch.empty(1, dtype=torch.int64, device=dev)
+    scr = torch.empty(int(_lib.lib.dll.pz_unwire_blocks_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+    sh = _lib.ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.lib.call("pz_dev_unwire_blocks", d_blocks.data_ptr(), d_offsets.data_ptr(), n, cap, _lib.ctypes.byref(c),
+                  natt.data_ptr(), scr.data_ptr(), sh)
+    out = {k: v[:size[k]] for k, v in cols.items()}
+    out["bytes_beg"] = out["bytes_beg"].view(n, 5)
+    out["bytes_len"] = out["bytes_len"].view(n, 5)
+    out["natt"] = natt
+    return out
