@@ -38,6 +38,7 @@
 #include "comm.h"
 #include "serial_hash.h"
 #include "epoch.h"
+#include "proto3_canon.h"
 #include "runtime.h"
 #include "votes.h"
 #include "wire.h"
@@ -185,60 +186,6 @@ static void put_msg(std::string& o, uint32_t f, const uint8_t* p, size_t n) {
   o.append((const char*)p, n);
 }
 
-// Streaming proto3 reader that also checks canonical form: the reference hashes
-// proto.Marshal of the DECODED message, so the engine accepts exactly the inputs that equal
-// the re-encoding of their own decoding.  Instead of re-encoding, every rule Marshal applies
-// is checked while reading: minimal varints (keys, values, lengths), ascending field numbers
-// (a repeated field only repeats in a run), zero scalars and empty singular bytes omitted,
-// a packed repeated field never empty, and no unknown fields.
-struct Reader {
-  const uint8_t* p;
-  const uint8_t* e;
-  bool ok = true;
-  bool more() const { return ok && p < e; }
-  // a minimal varint (a 10-byte one must end in 0x01: only bit 63 left)
-  uint64_t varint() {
-    uint64_t x = 0;
-    for (int i = 0, s = 0; i < 10; ++i, s += 7) {
-      if (p >= e) { ok = false; return 0; }
-      const uint8_t b = *p++;
-      x |= (uint64_t)(b & 0x7f) << s;
-      if (!(b & 0x80)) {
-        if ((i > 0 && b == 0) || (i == 9 && b != 1)) ok = false;
-        return x;
-      }
-    }
-    ok = false;
-    return 0;
-  }
-  bool span(const uint8_t** q, size_t* n) {
-    const uint64_t len = varint();
-    if (!ok || len > (uint64_t)(e - p)) { ok = false; return false; }
-    *q = p;
-    *n = (size_t)len;
-    p += len;
-    return true;
-  }
-  void skip(uint32_t wt) {  // (only for counting; canonical form is checked by the parsers)
-    const uint8_t* q;
-    size_t n;
-    if (wt == 0) varint();
-    else if (wt == 2) span(&q, &n);
-    else if (wt == 1 && e - p >= 8) p += 8;
-    else if (wt == 5 && e - p >= 4) p += 4;
-    else ok = false;
-  }
-  // the next key: field f with wire type wt, after field `prev`; `rep` = f may repeat
-  bool key(uint32_t prev, uint32_t* f, uint32_t* wt, uint32_t nfields, const uint32_t* types, uint32_t rep_mask) {
-    const uint64_t k = varint();
-    *f = (uint32_t)(k >> 3);
-    *wt = (uint32_t)(k & 7);
-    if (!ok || *f == 0 || *f > nfields || types[*f] != *wt) return ok = false;
-    if (*f < prev || (*f == prev && !((rep_mask >> *f) & 1))) return ok = false;
-    return true;
-  }
-};
-
 // The oblique parent hashes of one attestation: (offset, length) pairs into its encoding,
 // held in the call arena's pool.
 struct OblSpan {
@@ -312,44 +259,28 @@ struct CallArena {
   std::vector<Pool> obl;
 };
 
-// messages.pb.go:889-896: 1-3 varint, 4-6 bytes, 7 repeated bytes, 8 packed varints
-static bool parse_att(const uint8_t* p, size_t n, Att* a, CallArena::Pool& pool) {
-  static const uint32_t kTypes[9] = {9, 0, 0, 0, 2, 2, 2, 2, 2};
-  a->base = p;
-  a->len = (uint32_t)n;
-  a->obl_first = (uint32_t)pool.size();
-  const uint8_t* base = p;
-  Reader r{base, base + n};
-  uint32_t prev = 0, f, wt;
-  const uint8_t* q;
-  size_t len;
-  while (r.more()) {
-    if (!r.key(prev, &f, &wt, 8, kTypes, 1u << 7)) return false;
-    prev = f;
-    if (f <= 3) {
-      const uint64_t v = r.varint();
-      if (!v) return false;  // a zero scalar is omitted by Marshal
-      (f == 1 ? a->slot : f == 2 ? a->shard : a->jslot) = v;
-    } else if (!r.span(&q, &len)) {
-      return false;
-    } else if (f <= 6) {
-      if (!len) return false;  // an empty singular bytes field is omitted
-      if (f == 5) { a->sbh_off = (uint32_t)(q - base); a->sbh_len = (uint32_t)len; }
-      if (f == 6) { a->bf_off = (uint32_t)(q - base); a->bf_len = (uint32_t)len; }
-    } else if (f == 7) {
-      if (pool.size() == pool.capacity()) return false;  // (the bound makes this unreachable)
-      pool.push_back({(uint32_t)(q - base), (uint32_t)len});
-      ++a->obl.n;
-    } else {  // f == 8: packed, never empty
-      if (!len) return false;
-      Reader s{q, q + len};
-      while (s.more()) s.varint();
-      if (!s.ok) return false;
-    }
+// The engine's parser: proto3_canon.h's walks (the canonical-form rule) over the
+// pointer cursor, with visitors that fill Att, Block and the arena.
+struct AttVisit {
+  Att* a;
+  uint64_t at;  // the record's position in the cursor's input: Att's offsets count from it
+  CallArena::Pool& pool;
+  bool scalar(uint32_t f, uint64_t v) { (f == 1 ? a->slot : f == 2 ? a->shard : a->jslot) = v; return true; }
+  bool bytes(uint32_t f, uint64_t q, uint64_t len) {
+    if (f == 5) { a->sbh_off = (uint32_t)(q - at); a->sbh_len = (uint32_t)len; }
+    if (f == 6) { a->bf_off = (uint32_t)(q - at); a->bf_len = (uint32_t)len; }
+    return true;
   }
-  a->obl.p = pool.data() + a->obl_first;  // the pool never reallocates (reserved to a bound)
-  return r.ok;
-}
+  bool oblique(uint64_t q, uint64_t len) {
+    // Not part of the shared rule: the pool is this parser's storage, reserved to a bound that
+    // makes the check unreachable (it must not reallocate under Att::obl).
+    if (pool.size() == pool.capacity()) return false;
+    pool.push_back({(uint32_t)(q - at), (uint32_t)len});
+    ++a->obl.n;
+    return true;
+  }
+  bool sig(uint64_t) { return true; }
+};
 
 struct Block {
   const uint8_t* data;
@@ -359,51 +290,39 @@ struct Block {
   AttSpan atts;
 };
 
-// messages.pb.go:224-232: 1 bytes, 2 varint, 3-6 bytes, 7 Timestamp, 8 repeated records
 // Block i's records go to ar->atts[first[i], first[i+1]).
+struct BlockVisit {
+  Block* b;
+  CallArena* ar;
+  CallArena::Pool& pool;
+  uint64_t a0, a1;
+  bool scalar(uint32_t, uint64_t v) { b->slot = v; return true; }
+  bool bytes(uint32_t f, uint64_t q, uint64_t len) { if (f == 1) b->parent = copy32(b->data + q, len); return true; }
+  bool timestamp(int64_t, int64_t) { return true; }
+  bool record(const canon::PtrCursor& r, uint64_t q, uint64_t len) {
+    // Not part of the shared rule: the arena was sized by count_range, which counts what this
+    // walk visits, so the check is unreachable.
+    if (a0 + b->atts.n >= a1) return false;
+    Att* a = new (&ar->atts[a0 + b->atts.n]) Att();  // (constructed here, on the parsing thread)
+    a->base = b->data + q;
+    a->len = (uint32_t)len;
+    a->obl_first = (uint32_t)pool.size();
+    canon::PtrCursor s = r.sub(q, len);
+    if (!canon::walk_attestation(s, AttVisit{a, q, pool})) return false;
+    a->obl.p = pool.data() + a->obl_first;  // the pool never reallocates (reserved to a bound)
+    ar->ptrs[a0 + b->atts.n++] = a;
+    return true;
+  }
+};
+
 static bool parse_block(const uint8_t* p, size_t n, Block* b, CallArena* ar, uint64_t i, CallArena::Pool& pool) {
-  static const uint32_t kTypes[9] = {9, 2, 0, 2, 2, 2, 2, 2, 2};
-  static const uint32_t kTsTypes[3] = {9, 0, 0};
   b->data = p;
   b->len = n;
   const uint64_t a0 = ar->first[i], a1 = ar->first[i + 1];
   b->atts.p = ar->ptrs.data() + a0;
   b->atts.n = 0;
-  Reader r{p, p + n};
-  uint32_t prev = 0, f, wt;
-  const uint8_t* q;
-  size_t len;
-  while (r.more()) {
-    if (!r.key(prev, &f, &wt, 8, kTypes, 1u << 8)) return false;
-    prev = f;
-    if (f == 2) {
-      if (!(b->slot = r.varint())) return false;
-    } else if (!r.span(&q, &len)) {
-      return false;
-    } else if (f == 1 || f <= 6) {
-      if (!len) return false;
-      if (f == 1) b->parent = copy32(q, len);
-    } else if (f == 7) {  // Timestamp {int64 seconds = 1; int32 nanos = 2}; may be empty
-      Reader t{q, q + len};
-      uint32_t tp = 0, tf, twt;
-      while (t.more()) {
-        if (!t.key(tp, &tf, &twt, 2, kTsTypes, 0)) return false;
-        tp = tf;
-        const uint64_t v = t.varint();
-        if (!v) return false;
-        // int32: Marshal sign-extends the decoded 32-bit value
-        if (tf == 2 && v != (uint64_t)(int64_t)(int32_t)(uint32_t)v) return false;
-      }
-      if (!t.ok) return false;
-    } else {  // f == 8
-      if (a0 + b->atts.n >= a1) return false;  // more records than counted (unreachable)
-      Att* a = new (&ar->atts[a0 + b->atts.n]) Att();  // (constructed here, on the parsing thread)
-      if (!parse_att(q, len, a, pool)) return false;
-      ar->ptrs[a0 + b->atts.n] = a;
-      ++b->atts.n;
-    }
-  }
-  return r.ok && b->atts.n == a1 - a0;
+  canon::PtrCursor r{p, p, p + n, true};
+  return canon::walk_block(r, BlockVisit{b, ar, pool, a0, a1}) && b->atts.n == a1 - a0;
 }
 
 // ---- chain state ----------------------------------------------------------------------------
@@ -1452,17 +1371,6 @@ static uint32_t attester_committee(const Engine& g, const CState& C, const Att& 
   throw Rejected{PZ_ATT_NO_COMMITTEE};
 }
 
-// uvarint(x) at p (Go's binary.PutUvarint); returns the bytes written.
-static size_t put_uvarint(uint8_t* p, uint64_t x) {
-  size_t n = 0;
-  while (x >= 0x80) {
-    p[n++] = (uint8_t)(x | 0x80);
-    x >>= 7;
-  }
-  p[n++] = (uint8_t)x;
-  return n;
-}
-
 // What processAttestation found out about an attestation that calculateBlockVoteCache, run
 // next on the same block state, would compute again: its signed parent hashes (hash-log ids)
 // and its committee.
@@ -1489,8 +1397,8 @@ static void process_attestation(Engine& g, uint64_t block_slot, const Att& a, At
   // the message: a 10-byte buffer holding uvarint(slot % 64) overwritten by uvarint(shard)
   // at offset 0, then "parent ' '" x 64, then ShardBlockHash; assembled on the device
   uint8_t hdr[16] = {0};
-  put_uvarint(hdr, a.slot % kCycle);
-  put_uvarint(hdr, a.shard);
+  pz::put_varint(hdr, a.slot % kCycle);
+  pz::put_varint(hdr, a.shard);
   const size_t nobl = parents.obl.size(), vb = (4 * nobl + a.sbh_len + 3) & ~size_t(3);
   AttMsg* m = g.m_rec.grow(1);
   std::memcpy(m->hdr, hdr, sizeof m->hdr);
@@ -2270,7 +2178,7 @@ static int genesis(Engine& g) {
 
 // ---- reload: NewBeaconChain with a stored CrystallizedState (blockchain/core.go:86-95) -------
 // proto.Unmarshal accepts any valid encoding (field order, unpacked repeated scalars, unknown
-// fields), so this reader is lenient, unlike the canonical-only block Reader.
+// fields), so this reader is lenient, unlike the canonical-only walks of proto3_canon.h.
 struct LRd {
   const uint8_t* p;
   const uint8_t* e;
@@ -2459,10 +2367,10 @@ static std::shared_ptr<CallArena> make_arena(const uint64_t* offs, uint64_t n, s
 static uint64_t count_range(const uint8_t* data, const uint64_t* offs, uint64_t i0, uint64_t i1, uint64_t* cnt) {
   for (uint64_t i = i0; i < i1; ++i) {
     if (offs[i + 1] < offs[i]) return i;
-    Reader r{data + offs[i], data + offs[i + 1]};
+    canon::PtrCursor r{data, data + offs[i], data + offs[i + 1], true};
     uint64_t c = 0;
-    while (r.more()) {
-      const uint64_t key = r.varint();
+    while (r.ok && r.more()) {
+      const uint64_t key = canon::get_varint(r);
       if ((key >> 3) == 8 && (key & 7) == 2) ++c;
       r.skip((uint32_t)(key & 7));
     }
@@ -2922,8 +2830,8 @@ static void stage_digests_arena(const std::vector<Block>& blocks, uint64_t nb, u
         // overwritten by uvarint(shard), ShardBlockHash, each oblique hash copied into a [32]byte
         uint8_t* q = D.msgs.p + kpos;
         std::memset(q, 0, 10);
-        put_uvarint(q, a.slot);
-        put_uvarint(q, a.shard);
+        pz::put_varint(q, a.slot);
+        pz::put_varint(q, a.shard);
         std::memcpy(q + 10, a.at(a.sbh_off), a.sbh_len);
         uint64_t kl = 10 + a.sbh_len;
         for (auto& o : a.obl) {

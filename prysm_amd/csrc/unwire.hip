@@ -3,10 +3,9 @@
 //
 // Replaces golang/protobuf `proto.Unmarshal` at sync/service.go:147-164 (the received block,
 // messages.pb.go:224-232) with the records inside it (messages.pb.go:889-896), under the
-// engine's canonical-form rule (chain.hip parse_att / parse_block): an input is accepted only
-// if it is the encoding of its own decoding -- minimal varints, ascending fields (a repeated
-// field only repeats in a run), zero scalars and empty singular bytes absent, a packed field
-// never empty, no unknown fields.  A record that fails gets PZ_EINVAL and contributes nothing.
+// engine's canonical-form rule.  proto3_canon.h is the single statement of that rule; the walks
+// here are its visitors over the offset cursor, the engine's parser (chain.hip) its visitors
+// over the pointer cursor.  A record that fails gets PZ_EINVAL and contributes nothing.
 //
 // Each decode is three launches, one lane per record, 256 records per workgroup (a tile):
 //   size   walks the record, applies every rule, writes the fixed-size columns (scalars, status,
@@ -18,14 +17,14 @@
 // ticket and looks back; here the order between tiles is the order between launches), and the
 // second walk reads the bytes the first one judged, so it stays inside the record.
 //
-// Reads: only bytes of [begs[i], ends[i]).  Lengths are tested as `len > end - p`, so a
-// hostile length of 2^63 never wraps.  Writes: only inside the ranges the scans assign.
+// Reads: only bytes of [begs[i], ends[i]).  Writes: only inside the ranges the scans assign.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <mutex>
 #include <vector>
 
+#include "proto3_canon.h"
 #include "runtime.h"
 
 namespace pz {
@@ -36,81 +35,6 @@ constexpr int kScanThreads = 1024;
 constexpr int kAttCols = 7;  // d_totals' order: three bytes fields, elements, element bytes, sig values, bad records
 
 typedef __attribute__((address_space(1))) uint8_t gbyte;
-
-// A reader over d[p, e): chain.hip's Reader on offsets (no pointer is formed past the record).
-// Bytes come from a 16-byte window held in registers, loaded (unaligned) at min(pos, re - 16)
-// inside the record d[rb, re): a key with its length or value is one load, where a load per
-// varint byte was a dependent round trip each.  A record under 16 bytes, and WIN false (the A/B
-// library only), read byte by byte.
-template <bool WIN>
-struct Cur {
-  const uint8_t* d;
-  uint64_t p, e;
-  bool ok;
-  uint64_t rb, re;  // the record: what may be read
-  uint64_t w;       // the window holds d[w, w + 16) (w = re: nothing yet)
-  uint64_t lo, hi;
-};
-
-template <bool WIN>
-__device__ __forceinline__ Cur<WIN> cur_over(const uint8_t* d, uint64_t beg, uint64_t end) {
-  return Cur<WIN>{d, beg, end, true, beg, end, end, 0, 0};
-}
-
-// A reader over d[q, q + len) inside c's record; it starts with c's window.
-template <bool WIN>
-__device__ __forceinline__ Cur<WIN> cur_inside(const Cur<WIN>& c, uint64_t q, uint64_t len) {
-  Cur<WIN> s = c;
-  s.p = q;
-  s.e = q + len;
-  s.ok = true;
-  return s;
-}
-
-// The byte at pos, rb <= pos < re.
-template <bool WIN>
-__device__ __forceinline__ uint32_t byte_at(Cur<WIN>& c, uint64_t pos) {
-  if (!WIN || c.re - c.rb < 16) return c.d[pos];
-  if (pos - c.w >= 16) {  // (unsigned: a window after pos, or none yet, is far away too)
-    c.w = pos < c.re - 16 ? pos : c.re - 16;
-    uint2 v[2];
-    __builtin_memcpy(v, reinterpret_cast<const gbyte*>((uintptr_t)c.d) + c.w, 16);
-    c.lo = ((uint64_t)v[0].y << 32) | v[0].x;
-    c.hi = ((uint64_t)v[1].y << 32) | v[1].x;
-  }
-  const uint32_t off = (uint32_t)(pos - c.w);
-  return (uint32_t)((off < 8 ? c.lo >> (8 * off) : c.hi >> (8 * (off - 8))) & 0xff);
-}
-
-// a minimal varint (a 10-byte one must end in 0x01: only bit 63 left)
-template <bool WIN>
-__device__ __forceinline__ uint64_t get_varint(Cur<WIN>& c) {
-  uint64_t x = 0;
-  for (int i = 0, s = 0; i < 10; ++i, s += 7) {
-    if (c.p >= c.e) break;
-    const uint32_t b = byte_at(c, c.p++);
-    x |= (uint64_t)(b & 0x7f) << s;
-    if (!(b & 0x80)) {
-      if ((i > 0 && b == 0) || (i == 9 && b != 1)) c.ok = false;
-      return x;
-    }
-  }
-  c.ok = false;
-  return 0;
-}
-
-// a length and the bytes it covers: *q receives their start
-template <bool WIN>
-__device__ __forceinline__ uint64_t get_span(Cur<WIN>& c, uint64_t* q) {
-  const uint64_t len = get_varint(c);
-  if (!c.ok || len > c.e - c.p) {
-    c.ok = false;
-    return 0;
-  }
-  *q = c.p;
-  c.p += len;
-  return len;
-}
 
 // 16-byte unaligned pieces, the last one overlapping the one before it with the same bytes:
 // every load and store lies inside [0, len) (gfx950 runs unaligned global accesses).  PIECES
@@ -241,64 +165,55 @@ struct AttDst {
   uint64_t el, elb, sig;
 };
 
-// parse_att (chain.hip), to the letter: messages.pb.go:889-896, 1-3 varint, 4-6 bytes,
-// 7 repeated bytes, 8 packed varints.  W: also write the elements and the sig values.
+// The record's visitor: fields into AttRec.  W: also write the elements and the sig values.
+template <bool W, bool PIECES>
+struct AttVisit {
+  const AttArgs& a;
+  AttRec& r;
+  const AttDst& dst;
+  __device__ __forceinline__ bool scalar(uint32_t f, uint64_t v) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)  // (constant indices: the record stays in registers)
+      if (f == 1u + k) r.v[k] = v;
+    return true;
+  }
+  __device__ __forceinline__ bool bytes(uint32_t f, uint64_t q, uint64_t len) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      if (f == 4u + k) {
+        r.pos[k] = q;
+        r.len[k] = len;
+      }
+    return true;
+  }
+  __device__ __forceinline__ bool oblique(uint64_t q, uint64_t len) {
+    if (W) {
+      a.o.oblique_offs[dst.el + r.nel] = dst.elb + r.elb;
+      copy_span<PIECES>(a.o.oblique_parent_hashes + dst.elb + r.elb, a.d + q, len);
+    }
+    ++r.nel;
+    r.elb += len;
+    return true;
+  }
+  __device__ __forceinline__ bool sig(uint64_t x) {
+    if (W) a.o.aggregate_sig[dst.sig + r.nsig] = x;
+    ++r.nsig;
+    return true;
+  }
+};
+
 template <bool W, bool PIECES = true, bool WIN = true>
 __device__ __forceinline__ bool walk_att(const AttArgs& a, uint64_t beg, uint64_t end, AttRec& r, const AttDst& dst) {
   r = AttRec{};
   if (end < beg) return false;
-  Cur<WIN> c = cur_over<WIN>(a.d, beg, end);
+  canon::OffsetCursor<WIN> c = canon::OffsetCursor<WIN>::over(a.d, beg, end);
   if (a.field) {  // the frame: that field's key and a length that covers exactly the rest
-    const uint64_t k = get_varint(c);
+    const uint64_t k = canon::get_varint(c);
     if (!c.ok || k != (((uint64_t)a.field << 3) | 2)) return false;
-    const uint64_t len = get_varint(c);
-    if (!c.ok || len != c.e - c.p) return false;
+    const uint64_t len = canon::get_varint(c);
+    if (!c.ok || len != c.left()) return false;
   }
-  uint64_t prev = 0;
-  while (c.p < c.e) {
-    const uint64_t k = get_varint(c);
-    const uint64_t f = k >> 3;
-    if (!c.ok || f == 0 || f > 8 || (k & 7) != (f <= 3 ? 0u : 2u)) return false;
-    if (f < prev || (f == prev && f != 7)) return false;
-    prev = f;
-    if (f <= 3) {
-      const uint64_t v = get_varint(c);
-      if (!c.ok || !v) return false;  // a zero scalar is omitted by Marshal
-#pragma unroll
-      for (int k = 0; k < 3; ++k)  // (constant indices: the record stays in registers)
-        if (f == 1u + k) r.v[k] = v;
-      continue;
-    }
-    uint64_t q = 0;
-    const uint64_t len = get_span(c, &q);
-    if (!c.ok) return false;
-    if (f <= 6) {
-      if (!len) return false;  // an empty singular bytes field is omitted
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        if (f == 4u + k) {
-          r.pos[k] = q;
-          r.len[k] = len;
-        }
-    } else if (f == 7) {  // every element is emitted, an empty one too
-      if (W) {
-        a.o.oblique_offs[dst.el + r.nel] = dst.elb + r.elb;
-        copy_span<PIECES>(a.o.oblique_parent_hashes + dst.elb + r.elb, a.d + q, len);
-      }
-      ++r.nel;
-      r.elb += len;
-    } else {  // f == 8: packed, never empty, every varint whole and minimal
-      if (!len) return false;
-      Cur<WIN> s = cur_inside(c, q, len);
-      while (s.ok && s.p < s.e) {
-        const uint64_t x = get_varint(s);
-        if (W && s.ok) a.o.aggregate_sig[dst.sig + r.nsig] = x;
-        ++r.nsig;
-      }
-      if (!s.ok) return false;
-    }
-  }
-  return true;
+  return canon::walk_attestation(c, AttVisit<W, PIECES>{a, r, dst});
 }
 
 template <bool WIN>
@@ -440,64 +355,54 @@ struct BlockRec {
   uint64_t natt;
 };
 
-// parse_block's top level (chain.hip): messages.pb.go:224-232, 1 bytes, 2 varint, 3-6 bytes,
-// 7 Timestamp {int64 seconds = 1; int32 nanos = 2} (may be empty), 8 repeated records, jumped
-// over by their lengths.  W: also write the spans of the block's records, rows first + j.
+// The block's visitor: the top level into BlockRec.  W: also the records' spans, rows first + j.
+template <bool W>
+struct BlockVisit {
+  const BlockArgs& a;
+  BlockRec& r;
+  uint64_t i, first;
+  __device__ __forceinline__ bool scalar(uint32_t, uint64_t v) {
+    r.slot = v;
+    return true;
+  }
+  __device__ __forceinline__ bool bytes(uint32_t f, uint64_t q, uint64_t len) {
+    // Not part of the shared rule: bytes_len is a 32-bit column of this decoder alone (the
+    // engine's parser holds a block's length in a size_t and keeps no such column).
+    if (len > 0xffffffffull) return false;
+#pragma unroll
+    for (int s = 0; s < 5; ++s)  // fields 1, 3, 4, 5, 6 (constant indices: no private array)
+      if (f == (s ? s + 2u : 1u)) {
+        r.beg[s] = q;
+        r.len[s] = (uint32_t)len;
+      }
+    return true;
+  }
+  __device__ __forceinline__ bool timestamp(int64_t seconds, int64_t nanos) {
+    r.has_ts = true;
+    r.ts_seconds = seconds;
+    r.ts_nanos = nanos;
+    return true;
+  }
+  __device__ __forceinline__ bool record(const canon::OffsetCursor<true>&, uint64_t q, uint64_t len) {
+    const uint64_t row = first + r.natt;
+    if (W && row < a.att_cap) {
+      a.o.att_beg[row] = q;
+      a.o.att_end[row] = q + len;
+      a.o.att_block_slot[row] = r.slot;
+      a.o.att_block[row] = (uint32_t)i;
+    }
+    ++r.natt;
+    return true;
+  }
+};
+
 template <bool W>
 __device__ __forceinline__ bool walk_block(const BlockArgs& a, uint64_t i, uint64_t beg, uint64_t end, BlockRec& r,
                                            uint64_t first) {
   r = BlockRec{};
   if (end < beg) return false;
-  Cur<true> c = cur_over<true>(a.d, beg, end);
-  uint64_t prev = 0;
-  while (c.p < c.e) {
-    const uint64_t k = get_varint(c);
-    const uint64_t f = k >> 3;
-    if (!c.ok || f == 0 || f > 8 || (k & 7) != (f == 2 ? 0u : 2u)) return false;
-    if (f < prev || (f == prev && f != 8)) return false;
-    prev = f;
-    if (f == 2) {
-      if (!(r.slot = get_varint(c)) || !c.ok) return false;
-      continue;
-    }
-    uint64_t q = 0;
-    const uint64_t len = get_span(c, &q);
-    if (!c.ok) return false;
-    if (f <= 6) {
-      if (!len || len > 0xffffffffull) return false;  // (bytes_len is 32 bits)
-#pragma unroll
-      for (int s = 0; s < 5; ++s)  // fields 1, 3, 4, 5, 6 (constant indices: no private array)
-        if (f == (s ? s + 2u : 1u)) {
-          r.beg[s] = q;
-          r.len[s] = (uint32_t)len;
-        }
-    } else if (f == 7) {
-      r.has_ts = true;
-      Cur<true> t = cur_inside(c, q, len);
-      uint64_t tp = 0;
-      while (t.p < t.e) {
-        const uint64_t tk = get_varint(t);
-        const uint64_t tf = tk >> 3;
-        if (!t.ok || tf == 0 || tf > 2 || (tk & 7) != 0 || tf <= tp) return false;
-        tp = tf;
-        const uint64_t v = get_varint(t);
-        if (!t.ok || !v) return false;
-        // int32: Marshal sign-extends the decoded 32-bit value
-        if (tf == 2 && v != (uint64_t)(int64_t)(int32_t)(uint32_t)v) return false;
-        (tf == 1 ? r.ts_seconds : r.ts_nanos) = (int64_t)v;
-      }
-    } else {  // f == 8
-      const uint64_t row = first + r.natt;
-      if (W && row < a.att_cap) {
-        a.o.att_beg[row] = q;
-        a.o.att_end[row] = q + len;
-        a.o.att_block_slot[row] = r.slot;
-        a.o.att_block[row] = (uint32_t)i;
-      }
-      ++r.natt;
-    }
-  }
-  return true;
+  canon::OffsetCursor<true> c = canon::OffsetCursor<true>::over(a.d, beg, end);
+  return canon::walk_block(c, BlockVisit<W>{a, r, i, first});
 }
 
 extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_block_size_kernel(BlockArgs a) {

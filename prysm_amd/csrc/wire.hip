@@ -23,7 +23,7 @@
 
 #include <algorithm>
 
-
+#include "proto3_canon.h"  // put_varint
 #include "runtime.h"
 
 namespace pz {
@@ -39,15 +39,6 @@ constexpr int kBytesSub = 8, kBytesTileRecs = kBytesSub * kThreads;  // bytes-fi
 // varint length: (70 - clz) / 7 for 70 - clz in [6, 70] as a multiply by 37 and a shift (a
 // 24-bit multiply instead of the quarter-rate high multiply of a division by 7)
 __device__ __forceinline__ uint32_t vlen(uint64_t x) { return ((uint32_t)(70 - __clzll(x | 1)) * 37u) >> 8; }
-
-__device__ __forceinline__ uint8_t* put_varint(uint8_t* p, uint64_t x) {
-  while (x >= 0x80) {
-    *p++ = (uint8_t)(x | 0x80);
-    x >>= 7;
-  }
-  *p++ = (uint8_t)x;
-  return p;
-}
 
 __device__ __forceinline__ uint32_t frame_size(const WireValArgs& a, uint64_t body) {
   return (uint32_t)(a.field ? a.tag_len + vlen(body) + body : body);

@@ -29,6 +29,7 @@
 #include <rocprim/device/device_scan.hpp>
 #endif
 
+#include "proto3_canon.h"  // put_varint
 #include "runtime.h"
 
 namespace pz {
@@ -58,15 +59,6 @@ __device__ __forceinline__ uint32_t vlen(uint64_t x) { return (uint32_t)((70 - _
 // 32-bit values: one v_ffbh instead of two; (38 - clz) / 7 as a multiply by 37 and a shift
 // (exact for 38 - clz in [7, 38])
 __device__ __forceinline__ uint32_t vlen32(uint32_t x) { return ((38u - (uint32_t)__clz(x | 1)) * 37u) >> 8; }
-
-__device__ __forceinline__ uint8_t* put_varint(uint8_t* p, uint64_t x) {
-  while (x >= 0x80) {
-    *p++ = (uint8_t)(x | 0x80);
-    x >>= 7;
-  }
-  *p++ = (uint8_t)x;
-  return p;
-}
 
 // put_varint into the LDS stage with at most four stores (8-, 4-, 2- and 1-byte pieces,
 // unaligned): x's 7-bit groups spread into three dwords by bit-field extracts, the

@@ -1,28 +1,18 @@
 """The block engine accepts exactly the canonical proto3 encodings: the
 reference hashes proto.Marshal of the DECODED block (types/block.go:69), so an input that is
 not the canonical encoding of its own decoding would hash differently from its bytes; the
-engine rejects it with PZ_EINVAL instead of guessing.  Each case below is a decodable
-BeaconBlock whose re-encoding differs from its bytes (or, for the accepted cases, does not),
-decided here independently by Google's protobuf runtime over the oracle schema."""
+engine rejects it with PZ_EINVAL instead of guessing.  Each case (tests/canon_corpus.py) is a
+decodable BeaconBlock whose re-encoding differs from its bytes (or, for the accepted cases, does
+not), decided here independently by Google's protobuf runtime over the oracle schema."""
 import numpy as np
 import pytest
 
+from canon_corpus import CANONICAL, NONCANONICAL, UNKNOWN_FIELD_BLOCK
 from oracle import schema as opb
-from prysm_amd import _lib, pb, wire
+from prysm_amd import _lib
 from prysm_amd.blockchain import BeaconChain
 
 pytestmark = pytest.mark.gpu
-
-ATT = pb.AttestationRecord(slot=0, shard_id=3, justified_slot=0, shard_block_hash=b"\x11" * 32,
-                           attester_bitfield=b"\xff\x00", oblique_parent_hashes=[b"\x22" * 32], aggregate_sig=[5, 7])
-
-
-def block(atts=(ATT,), ts=pb.Timestamp(8, 0)):
-    return pb.BeaconBlock(parent_hash=b"\x01" * 32, slot_number=1, timestamp=ts, attestations=list(atts))
-
-
-def frame(num, body):
-    return wire._msg(num, body)
 
 
 def canonical_by_runtime(raw):
@@ -35,40 +25,6 @@ def run(raw):
     data = np.frombuffer(raw + bytes(16), dtype=np.uint8)
     offs = np.array([0, len(raw)], dtype=np.uint64)
     BeaconChain(1024).process_serialized(data, offs)
-
-
-def att_bytes(**over):
-    a = pb.AttestationRecord(**{**ATT.__dict__, **over})
-    return wire.attestation_record(a)
-
-
-E = wire.beacon_block(block())
-HEAD = E[:E.index(b"\x42")]  # everything before the attestation field
-A = wire.attestation_record(ATT)
-
-NONCANONICAL = {
-    "slot field repeated at the end": E + b"\x10\x01",
-    "non-minimal varint (slot)": E.replace(b"\x10\x01", b"\x10\x81\x00", 1),
-    "fields out of order": E.replace(b"\x10\x01", b"", 1) + b"\x10\x01",
-    "explicit empty bytes (randao_reveal)": E.replace(b"\x10\x01", b"\x10\x01\x1a\x00", 1),
-    "explicit zero scalar in the timestamp": E.replace(b"\x3a\x02\x08\x08", b"\x3a\x04\x08\x08\x10\x00", 1),
-    "timestamp nanos beyond int32 (Marshal re-encodes the truncated int32)":
-        E.replace(b"\x3a\x02\x08\x08", b"\x3a\x08\x08\x08\x10" + wire.varint((1 << 32) + 5), 1),
-    "attestation: explicit zero slot": HEAD + frame(8, b"\x08\x00" + A),
-    "attestation: field 7 run broken by field 8 then 7 again": HEAD + frame(8, A + wire._msg(7, b"\x33" * 32)),
-    "attestation: empty packed signature": HEAD + frame(8, A + b"\x42\x00"),
-    "attestation: non-minimal length prefix": HEAD + b"\x42" + bytes([0x80 | len(A), 0x00]) + A
-    if len(A) < 128 else None,
-}
-CANONICAL = {
-    "as encoded": E,
-    "empty oblique element (every element is emitted)": wire.beacon_block(block(
-        [pb.AttestationRecord(**{**ATT.__dict__, "oblique_parent_hashes": [b""]})])),
-    "empty timestamp message (a set message is emitted)": wire.beacon_block(block(ts=pb.Timestamp(0, 0))),
-    "no attestations": wire.beacon_block(block(atts=())),
-    "negative timestamp seconds (10-byte varint)": wire.beacon_block(block(ts=pb.Timestamp(-5, 0))),
-    "negative nanos (sign-extended 10-byte varint)": wire.beacon_block(block(ts=pb.Timestamp(1, -3))),
-}
 
 
 @pytest.mark.parametrize("name", [k for k, v in NONCANONICAL.items() if v is not None])
@@ -92,7 +48,7 @@ def test_unknown_fields_rejected():
     XXX_unrecognized and re-emits it at the end, so Marshal(decode(x)) == x there; the engine
     does not model unrecognized fields and rejects the block (PZ_EINVAL) rather than hash
     bytes it does not understand."""
-    raw = E + b"\x48\x01"
+    raw = UNKNOWN_FIELD_BLOCK
     assert canonical_by_runtime(raw)
     with pytest.raises(_lib.PzError) as e:
         run(raw)

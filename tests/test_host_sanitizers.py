@@ -1,6 +1,7 @@
 """Host code under sanitizers (SURVEY.md §5 race detection): the serial BLAKE2b hasher and its
-thread pool (prysm_amd/csrc/serial_hash.cpp) built with ASan+UBSan and with TSan by
-``make -C prysm_amd/csrc san``, run on the CPU.  No GPU code is involved."""
+thread pool (prysm_amd/csrc/serial_hash.cpp) built with ASan+UBSan and with TSan, and the
+canonical-form rule's walks over both cursors (prysm_amd/csrc/proto3_canon.h) built with
+ASan+UBSan, by ``make -C prysm_amd/csrc san``, run on the CPU.  No GPU code is involved."""
 import os
 import platform
 import shutil
@@ -35,3 +36,16 @@ def test_serial_hasher_clean_under_sanitizer(san_build, kind):
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.startswith("ok"), r.stdout
     assert "ERROR" not in r.stderr and "WARNING: ThreadSanitizer" not in r.stderr, r.stderr
+
+
+def test_canonical_walks_clean_and_consistent_under_sanitizer(san_build, tmp_path):
+    """Both cursors over the whole corpus, each case with the protobuf runtime's verdict, and
+    over the program's mutants of the canonical cases (prysm_amd/csrc/tests/proto3_canon_san.cpp)."""
+    from canon_corpus import san_corpus_file
+
+    corpus = tmp_path / "canon_corpus.bin"
+    corpus.write_bytes(san_corpus_file())
+    r = subprocess.run([os.path.join(san_build, "san_canon"), str(corpus)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("ok"), r.stdout
+    assert "ERROR" not in r.stderr, r.stderr

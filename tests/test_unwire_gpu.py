@@ -1,25 +1,24 @@
 """Device proto3 decoder (prysm_amd/csrc/unwire.hip): AttestationRecords back into the columns
 of pz_attestation_cols, and the top level of serialized BeaconBlocks.
 
-What "canonical" means is decided here by Google's protobuf runtime over the oracle schema
-(oracle/schema.py), independently of the code under test: a record is canonical iff it parses,
-holds no unknown field and serializes back to the same bytes.  Decoded fields are compared with
-the runtime's parse of the same bytes, and with the device encoder (wire_att.hip) both ways."""
+What "canonical" means is decided (tests/canon_corpus.py) by Google's protobuf runtime over the
+oracle schema (oracle/schema.py), independently of the code under test: a record is canonical
+iff it parses, holds no unknown field and serializes back to the same bytes.  Decoded fields are
+compared with the runtime's parse of the same bytes, and with the device encoder (wire_att.hip)
+both ways."""
 import ctypes
 import functools
 import hashlib
 
 import numpy as np
 import pytest
-from google.protobuf import unknown_fields
-from google.protobuf.message import DecodeError
 
+from canon_corpus import CANONICAL, CANONICAL_CASES, CORPUS, FRAMED, NONCANONICAL, UNKNOWN_FIELD_BLOCK, canonical
 from oracle import ref
 from oracle import schema as opb
 from prysm_amd import _lib, pb, synth, wire
 from prysm_amd.blockchain import check_attestations, check_serialized_blocks, serialize_blocks
 from test_attcheck_gpu import random_batch, table
-from test_canonical_gpu import CANONICAL, NONCANONICAL, E
 from test_wire import rand_att
 
 pytestmark = pytest.mark.gpu
@@ -35,19 +34,6 @@ PER_RECORD = ("slot", "shard_id", "justified_slot", "n_oblique", "last_byte", "s
 
 
 # ---- the oracle ---------------------------------------------------------------------------------
-def has_unknown(m):
-    return bool(len(unknown_fields.UnknownFieldSet(m))) or any(has_unknown(a) for a in getattr(m, "attestations", ()))
-
-
-def canonical(raw, cls=opb.AttestationRecord):
-    m = cls()
-    try:
-        m.ParseFromString(raw)
-    except DecodeError:
-        return False
-    return not has_unknown(m) and m.SerializeToString() == raw
-
-
 def parse(raw):
     m = opb.AttestationRecord()
     m.ParseFromString(raw)
@@ -127,40 +113,7 @@ def test_inverse_of_the_encoder(n):
     np.testing.assert_array_equal(offs2, np.arange(n + 1, dtype=U64) * U64(512))
 
 
-# ---- 3. the non-canonical corpus ----------------------------------------------------------------
-BASE = pb.AttestationRecord(slot=5, shard_id=300, justified_slot=1 << 40, justified_block_hash=b"\x11" * 32,
-                            shard_block_hash=b"\x22" * 32, attester_bitfield=b"\xff\x80",
-                            oblique_parent_hashes=[b"\x33" * 32, b""], aggregate_sig=[5, (1 << 64) - 1])
-A = wire.attestation_record(BASE)
-CORPUS = {
-    "as encoded": A,
-    "10-byte varint ending 0x01": b"\x08" + b"\xff" * 9 + b"\x01",
-    "the empty record": b"",
-    "empty field-7 element": b"\x3a\x00",
-    "truncated by one byte": A[:-1],
-    "10-byte varint ending 0x02": b"\x08" + b"\xff" * 9 + b"\x02",
-    "11-byte varint": b"\x08" + b"\xff" * 10 + b"\x01",
-    "08 85 00": b"\x08\x85\x00",
-    "08 00": b"\x08\x00",
-    "field 9 appended": A + b"\x48\x01",
-    "field 1 with wire type 2": b"\x0a\x01\x00",
-    "field 8 unpacked": b"\x40\x05",
-    "2a 05 01 (length past the end)": b"\x2a\x05\x01",
-    "a length of 2^63": b"\x2a" + wire.varint(1 << 63) + b"\x01\x02",
-    "field number 0": b"\x00\x01",
-    "42 01 80 (packed varint cut)": b"\x42\x01\x80",
-    "10 01 08 01 (order)": b"\x10\x01\x08\x01",
-    "08 01 08 02 (repeat)": b"\x08\x01\x08\x02",
-    "2a 00": b"\x2a\x00",
-    "field-7 run broken by field 8 and resumed": b"\x3a\x01\xaa\x42\x01\x05\x3a\x01\xbb",
-}
-CANONICAL_CASES = {"as encoded", "10-byte varint ending 0x01", "the empty record", "empty field-7 element"}
-FRAMED = {name: wire._msg(8, c) for name, c in CORPUS.items()}
-FRAMED.update({
-    "non-minimal frame length": b"\x42\x82\x00\x08\x01",
-    "frame length one short of the span": b"\x42\x01\x08\x01",
-    "frame length one long of the span": b"\x42\x03\x08\x01",
-})
+# ---- 3. the non-canonical corpus (tests/canon_corpus.py) ----------------------------------------
 NEIGHBOURS = rand_records(7)[:6]
 
 
@@ -392,7 +345,7 @@ def test_folded_status_is_the_engines_verdict():
     want.update({k: _lib.PZ_OK for k in CANONICAL})
     want["unknown field 9 appended"] = _lib.PZ_EINVAL
     raws = {**{k: v for k, v in NONCANONICAL.items() if v is not None}, **CANONICAL,
-            "unknown field 9 appended": E + b"\x48\x01"}
+            "unknown field 9 appended": UNKNOWN_FIELD_BLOCK}
     assert dict(zip(raws, folded_status(list(raws.values())))) == want
     assert {k: folded_status([v])[0] for k, v in raws.items()} == want
 
