@@ -715,6 +715,53 @@ typedef struct pz_att_check_batch {
 int pz_check_attestations(const pz_att_check_batch* b);                  /* host pointers */
 int pz_dev_check_attestations(const pz_att_check_batch* b, void* stream); /* device pointers */
 
+/* ---- H: Attestation.Key and the processAttestation message digest from device columns ----
+ * The two digests of blockProcessing whose messages are not a span of the received bytes;
+ * neither message is materialised: one GPU lane per attestation assembles it block by block
+ * from the columns pz_dev_unwire_attestations leaves on the device.  Memory contract: 4
+ * readable bytes past the last byte of every bytes column (the CSR hash form's).
+ *
+ * pz_dev_attestation_keys replaces (*Attestation).Key, types/attestation.go:61-77 (the DB key
+ * of saveAttestation): blake2b.Sum512 of
+ *   key[0:10] (PutUvarint(Slot) at 0, then PutUvarint(ShardId) at 0 over it)
+ *   | ShardBlockHash (its full length) | copy into [32]byte of each ObliqueParentHashes element
+ * truncated to out_bytes (32: what Key returns; 64: the whole Sum512).  Of `a` it reads slot,
+ * shard_id, shard_block_hash(+_offs) and the three oblique columns, with pz_attestation_cols'
+ * NULL rules (a NULL scalar is 0 everywhere, NULL offsets are empty ranges).  A row with
+ * d_rec_status[i] != PZ_OK (optional: pz_attestation_cols_out.status) gets a zero key.
+ * PZ_EINVAL, before any launch: out_bytes other than 32 or 64; with n > 0 a NULL a or d_out,
+ * offsets without their data column, d_out not 16-byte aligned.  n == 0 launches nothing. */
+int pz_dev_attestation_keys(const pz_attestation_cols* a, uint64_t n, const int32_t* d_rec_status /* optional */,
+                            uint8_t* d_out, uint32_t out_bytes /* 32 | 64 */, void* stream);
+int pz_attestation_keys(const pz_attestation_cols* a, uint64_t n, uint8_t* out, uint32_t out_bytes);  /* host, sync */
+
+/* pz_dev_attestation_messages replaces the message assembly and hash of processAttestation,
+ * blockchain/core.go:277-290, with getSignedParentHashes' result (:348-360) taken as
+ * parents_start: for every row whose status is PZ_ATT_PROCESSED, out[64 i ..] = blake2b.Sum512 of
+ *   msg[0:10] (PutUvarint(Slot % 64) at 0, then PutUvarint(ShardId) at 0 over it)
+ *   | for r < 64: parent_r | ' ' | ShardBlockHash
+ * where parent_r = recent[parents_start[i] + r] for r < 64 - m and the record's m oblique
+ * elements under common.BytesToHash after them; msg_len[i] = 2122 + len(ShardBlockHash).  A row
+ * with any other status gets a zero digest and msg_len 0, and nothing is read through its
+ * parents_start; so does a PROCESSED row whose m > 64 or whose parents would leave recent
+ * (pz_dev_check_attestations never reports one).
+ * PZ_EINVAL, before any launch: with natt > 0 a NULL status, parents_start or out, offsets
+ * without their data column, n_recent < 64 (or a NULL recent) while a row is PROCESSED.  The
+ * device form cannot see the statuses before it launches, so it applies that last rule to every
+ * non-empty batch, and wants out 16-byte aligned.  natt == 0 launches nothing. */
+typedef struct pz_att_msg_batch {   /* every member a pointer or a uint64_t */
+  uint64_t natt;
+  const uint64_t *slot, *shard_id;
+  const uint8_t* shard_block_hash;      const uint64_t* shard_block_hash_offs;
+  const uint8_t* oblique_parent_hashes; const uint64_t *oblique_offs, *oblique_first;
+  const int32_t*  status;               /* pz_att_check_batch.status */
+  const uint64_t* parents_start;        /* pz_att_check_batch.parents_start */
+  const uint8_t*  recent; uint64_t n_recent;   /* RecentBlockHashes(), n_recent x 32 B, already BytesToHash-normalised */
+  uint8_t* out;  /* natt x 64 */   uint32_t* msg_len;  /* optional */
+} pz_att_msg_batch;
+int pz_dev_attestation_messages(const pz_att_msg_batch* b, void* stream);
+int pz_attestation_messages(const pz_att_msg_batch* b);   /* host pointers, sync */
+
 typedef struct pz_block_result {
   uint8_t hash[32];      /* Block.Hash() */
   int32_t status;        /* PZ_BLOCK_* */

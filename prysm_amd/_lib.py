@@ -104,6 +104,10 @@ SIGNATURES = {
     "pz_dev_unwire_blocks": [vp, vp, u64, u64, vp, vp, vp, vp],
     "pz_unwire_blocks": [vp, vp, u64, u64, vp, c_u64p],
     "pz_dev_check_attestations": [vp, vp],
+    "pz_dev_attestation_keys": [vp, u64, vp, vp, u32, vp],
+    "pz_attestation_keys": [vp, u64, vp, u32],
+    "pz_dev_attestation_messages": [vp, vp],
+    "pz_attestation_messages": [vp],
     "pz_shutdown": [],
     "pz_state_new": [u64, ctypes.c_int, vp],
     "pz_state_upload": [vp, vp, vp, vp],
@@ -227,6 +231,15 @@ class AttCheckBatch(ctypes.Structure):
         ("last_state_recalc", u64), ("n_recent", u64), ("narr", u64), ("arr_offs", vp), ("arr_shard", vp),
         ("arr_comm", vp), ("coffs", vp), ("status", vp), ("committee", vp), ("parents_start", vp),
         ("last_byte", vp),
+    ]
+
+
+class AttMsgBatch(ctypes.Structure):
+    """Mirror of ``pz_att_msg_batch`` (include/prysm_hip.h)."""
+    _fields_ = [
+        ("natt", u64), ("slot", vp), ("shard_id", vp), ("shard_block_hash", vp), ("shard_block_hash_offs", vp),
+        ("oblique_parent_hashes", vp), ("oblique_offs", vp), ("oblique_first", vp), ("status", vp),
+        ("parents_start", vp), ("recent", vp), ("n_recent", u64), ("out", vp), ("msg_len", vp),
     ]
 
 

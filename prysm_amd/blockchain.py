@@ -140,6 +140,133 @@ def check_serialized_blocks(data, offsets, last_justified_slot, last_state_recal
             pstart[:natt].cpu().numpy().view(np.uint64))
 
 
+_MSG_COLS = ("slot", "shard_id", "shard_block_hash", "shard_block_hash_offs", "oblique_parent_hashes", "oblique_offs",
+             "oblique_first")
+
+
+def _recent_array(recent_hashes):
+    """RecentBlockHashes() (types/state.go:189-195: every entry under BytesToHash) as (k, 32) uint8."""
+    if isinstance(recent_hashes, np.ndarray):
+        return np.ascontiguousarray(recent_hashes, dtype=np.uint8).reshape(-1, 32)
+    from prysm_amd.types import bytes_to_hash
+    return np.frombuffer(b"".join(bytes_to_hash(h) for h in recent_hashes), dtype=np.uint8).reshape(-1, 32)
+
+
+def attestation_messages(cols, n, status, parents_start, recent_hashes):
+    """The processAttestation message digests (blockchain/core.go:277-290) of n records held as
+    host columns (numpy arrays keyed as ``wire.ATT_COLS``), with ``status`` / ``parents_start`` as
+    :func:`check_attestations` returns them and ``recent_hashes`` = RecentBlockHashes() (a list
+    of byte strings, normalised here, or a (k, 32) uint8 array): ``pz_attestation_messages``.
+    Returns ``(digests (n, 64) uint8, msg_len (n) uint32)``; a row that is not PROCESSED has a
+    zero digest and length 0."""
+    keep = {k: np.ascontiguousarray(cols[k]) for k in _MSG_COLS if cols.get(k) is not None}
+    status = np.ascontiguousarray(status, dtype=np.int32)
+    pstart = np.ascontiguousarray(parents_start, dtype=np.uint64)
+    recent = _recent_array(recent_hashes)
+    out = np.zeros((n, 64), dtype=np.uint8)
+    mlen = np.zeros(n, dtype=np.uint32)
+    b = _lib.AttMsgBatch(natt=n, status=_lib.ptr(status), parents_start=_lib.ptr(pstart), recent=_lib.ptr(recent),
+                         n_recent=len(recent), out=_lib.ptr(out), msg_len=_lib.ptr(mlen),
+                         **{k: v.ctypes.data for k, v in keep.items()})
+    lib.call("pz_attestation_messages", ctypes.byref(b))
+    return out, mlen
+
+
+def attestation_messages_device(cols, n, status, parents_start, recent, n_recent=None):
+    """:func:`attestation_messages` on device columns (torch tensors keyed as ``wire.ATT_COLS``,
+    e.g. from ``wire.unwire_attestations_device``; ``status`` int32, ``parents_start`` int64 and
+    ``recent`` ((k, 32) uint8, already BytesToHash-normalised) tensors too), on the current
+    stream: ``pz_dev_attestation_messages``.  Returns ``(digests (n, 64) uint8, msg_len (n)
+    int32)`` tensors; nothing visits the host."""
+    import torch
+
+    dev = status.device
+    out = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+    mlen = torch.empty(n, dtype=torch.int32, device=dev)
+    b = _lib.AttMsgBatch(natt=n, status=status.data_ptr(), parents_start=parents_start.data_ptr(),
+                         recent=recent.data_ptr() if recent.numel() else None,
+                         n_recent=recent.numel() // 32 if n_recent is None else n_recent,
+                         out=out.data_ptr() if n else None, msg_len=mlen.data_ptr() if n else None,
+                         **{k: cols[k].data_ptr() for k in _MSG_COLS if cols.get(k) is not None})
+    lib.call("pz_dev_attestation_messages", ctypes.byref(b), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    return out, mlen
+
+
+def digest_serialized_blocks(data, offsets, last_justified_slot, last_state_recalc, n_recent, shard_and_committees,
+                             recent_hashes, device=0):
+    """The H side of blockProcessing (blockchain/service.go:229-363) for a batch of received
+    blocks held as bytes, against one chain state: after one upload the bytes are split
+    (``pz_dev_unwire_blocks``), decoded (``pz_dev_unwire_attestations``) and checked
+    (``pz_dev_check_attestations``) as in :func:`check_serialized_blocks`, then hashed where they
+    lie (``pz_dev_blake2b512_spans``: Block.Hash over the blocks, Attestation.Hash over the
+    records' spans) and ``Key`` and the processAttestation message digest are made from the
+    decoded columns (``pz_dev_attestation_keys``, ``pz_dev_attestation_messages``).  No column
+    visits the host in between (only the attestation count does, to size the launches).
+
+    ``recent_hashes``: RecentBlockHashes() (``n_recent`` entries: byte strings, normalised here,
+    or a (n_recent, 32) uint8 array).  Returns a dict of numpy arrays: ``block_status`` (PZ_OK /
+    PZ_EINVAL as check_serialized_blocks folds it), ``block_hash`` (n, 32), ``att_first`` (n+1),
+    ``att_status`` and, per attestation, ``hash`` (32), ``key`` (32; zero where the record is not
+    canonical), ``msg`` (64) and ``msg_len`` (zero where the attestation is not PROCESSED)."""
+    import torch
+
+    from prysm_amd import types
+
+    dev = torch.device("cuda", device)
+    data = np.ascontiguousarray(_lib.as_u8(data), dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    recent = _recent_array(recent_hashes)
+    if len(recent) != n_recent:
+        raise PzError(_lib.PZ_EINVAL, "recent_hashes holds %d hashes, n_recent is %d" % (len(recent), n_recent))
+
+    def up(a):
+        a = a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32) if a.dtype == np.uint32 else a
+        with warnings.catch_warnings():  # (a read-only source, e.g. np.frombuffer: it is only copied from)
+            warnings.simplefilter("ignore", UserWarning)
+            return torch.from_numpy(a).to(dev)
+
+    # (the span hash reads whole dwords: 4 bytes of slack after the last block)
+    d_bytes = up(np.concatenate([data[:int(offsets[-1])] if n else data[:0], np.zeros(4, np.uint8)]))
+    d_offs = up(offsets)
+    sh = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    blk = wire.unwire_blocks_device(d_bytes, d_offs, n)
+    natt = int(blk["natt"].item())
+    att = wire.unwire_attestations_device(d_bytes, blk["att_beg"], blk["att_end"], natt, 0)
+    table = [up(a) for a in _committee_table(shard_and_committees)]
+    status = torch.zeros(max(natt, 1), dtype=torch.int32, device=dev)
+    pstart = torch.zeros(max(natt, 1), dtype=torch.int64, device=dev)
+    b = _lib.AttCheckBatch(
+        natt, att["slot"].data_ptr(), att["justified_slot"].data_ptr(), att["shard_id"].data_ptr(),
+        att["n_oblique"].data_ptr(), att["attester_bitfield"].data_ptr(), att["attester_bitfield_offs"].data_ptr(),
+        blk["att_block_slot"].data_ptr(), last_justified_slot, last_state_recalc, n_recent,
+        len(shard_and_committees), *[t.data_ptr() for t in table], status.data_ptr(), None, pstart.data_ptr(),
+        att["last_byte"].data_ptr())
+    lib.call("pz_dev_check_attestations", ctypes.byref(b), sh)
+    rec = att["status"][:natt]
+    status = torch.where(rec != 0, rec, status[:natt])
+    block_status = wire.folded_block_status(blk["status"], blk["att_block"][:natt], rec)
+
+    block_hash = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    att_hash = torch.empty((natt, 32), dtype=torch.uint8, device=dev)
+    lib.call("pz_dev_blake2b512_spans", d_bytes.data_ptr(), d_offs[:-1].data_ptr(), d_offs[1:].data_ptr(), n,
+             block_hash.data_ptr() if n else None, 32, sh)
+    lib.call("pz_dev_blake2b512_spans", d_bytes.data_ptr(), blk["att_beg"].data_ptr(), blk["att_end"].data_ptr(), natt,
+             att_hash.data_ptr() if natt else None, 32, sh)
+    key = types.attestation_keys_device(att, natt, rec_status=rec if natt else None)
+    if natt and n_recent < 64 and (status == ATT_PROCESSED).any().item():  # (an m > 0 row can pass with fewer)
+        raise PzError(_lib.PZ_EINVAL, "n_recent %d < 64 with a PROCESSED attestation" % n_recent)
+    if natt and n_recent >= 64:
+        msg, msg_len = attestation_messages_device(att, natt, status.contiguous(), pstart, up(recent), n_recent)
+    else:
+        msg = torch.zeros((natt, 64), dtype=torch.uint8, device=dev)
+        msg_len = torch.zeros(natt, dtype=torch.int32, device=dev)
+    return {"block_status": block_status.cpu().numpy(), "block_hash": block_hash.cpu().numpy(),
+            "att_first": blk["att_first"].cpu().numpy().view(np.uint64), "att_status": status.cpu().numpy(),
+            "hash": att_hash.cpu().numpy(), "key": key.cpu().numpy(), "msg": msg.cpu().numpy(),
+            "msg_len": msg_len.cpu().numpy().view(np.uint32)}
+
+
 class ChainPanic(RuntimeError):
     """The reference would panic here (index out of range / nil map / nil state)."""
 

@@ -110,6 +110,38 @@ def attestation_keys(atts):
     return _hash_many([a.key_bytes() for a in atts])
 
 
+_KEY_COLS = ("slot", "shard_id", "shard_block_hash", "shard_block_hash_offs", "oblique_parent_hashes",
+             "oblique_offs", "oblique_first")
+
+
+def attestation_keys_columns(cols, n, out_bytes=32):
+    """``Key()`` (attestation.go:61-77) of n records held as host columns (numpy arrays keyed as
+    ``wire.ATT_COLS``; see ``wire.attestation_columns``): ``pz_attestation_keys`` assembles and
+    hashes the key bytes on the GPU, one lane per record.  Returns (n, out_bytes) uint8."""
+    keep = {k: np.ascontiguousarray(cols[k]) for k in _KEY_COLS if cols.get(k) is not None}
+    c = _lib.AttestationCols(**{k: v.ctypes.data for k, v in keep.items()})
+    out = np.zeros((n, out_bytes), dtype=np.uint8)
+    _lib.lib.call("pz_attestation_keys", _lib.ctypes.byref(c), n, out.ctypes.data if n else None, out_bytes)
+    return out
+
+
+def attestation_keys_device(cols, n, rec_status=None, out_bytes=32):
+    """``Key()`` (attestation.go:61-77) of n records held as device columns (torch tensors keyed
+    as ``wire.ATT_COLS``, e.g. what ``wire.unwire_attestations_device`` returns; every bytes
+    column with 4 readable bytes after its last byte), on the current stream:
+    ``pz_dev_attestation_keys``.  ``rec_status`` (int32 tensor, optional): rows whose status is
+    not PZ_OK get a zero key.  Returns an (n, out_bytes) uint8 tensor; nothing visits the host."""
+    import torch
+
+    dev = next(v for v in cols.values() if hasattr(v, "data_ptr")).device
+    c = _lib.AttestationCols(**{k: cols[k].data_ptr() for k in _KEY_COLS if cols.get(k) is not None})
+    out = torch.empty((n, out_bytes), dtype=torch.uint8, device=dev)
+    _lib.lib.call("pz_dev_attestation_keys", _lib.ctypes.byref(c), n,
+                  rec_status.data_ptr() if rec_status is not None else None, out.data_ptr() if n else None,
+                  out_bytes, _lib.ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
 class ActiveState:
     """types/state.go:14-19 (+ the block vote cache, kept by the caller)."""
 
