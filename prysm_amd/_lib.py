@@ -108,6 +108,13 @@ SIGNATURES = {
     "pz_attestation_keys": [vp, u64, vp, u32],
     "pz_dev_attestation_messages": [vp, vp],
     "pz_attestation_messages": [vp],
+    "pz_vote_cache_new": [u64, u32, ctypes.c_int, vp],
+    "pz_vote_cache_free": [vp],
+    "pz_vote_cache_scratch_bytes": [u64, u64, u64],
+    "pz_dev_vote_cache_tally": [vp, vp, vp, vp],
+    "pz_vote_cache_tally": [vp, vp],
+    "pz_vote_cache_read": [vp, vp, vp, u64, c_u64p],
+    "pz_vote_cache_voters": [vp, vp, vp, c_intp],
     "pz_shutdown": [],
     "pz_state_new": [u64, ctypes.c_int, vp],
     "pz_state_upload": [vp, vp, vp, vp],
@@ -243,6 +250,16 @@ class AttMsgBatch(ctypes.Structure):
     ]
 
 
+class VoteColsBatch(ctypes.Structure):
+    """Mirror of ``pz_vote_cols_batch`` (include/prysm_hip.h)."""
+    _fields_ = [
+        ("natt", u64), ("n_oblique", vp), ("oblique_parent_hashes", vp), ("oblique_offs", vp), ("oblique_first", vp),
+        ("n_oblique_total", u64), ("bits", vp), ("boffs", vp), ("status", vp), ("committee", vp),
+        ("parents_start", vp), ("take", vp), ("recent", vp), ("n_recent", u64), ("members", vp), ("coffs", vp),
+        ("ncomm", u64), ("balance", vp),
+    ]
+
+
 SCAL_POP, SCAL_NACT, SCAL_ERR_XL, SCAL_ERR_RWD, SCAL_APPLIED, SCAL_NEXT_BAL, SCAL_MAXIDX1, SCAL_NOMATCH = range(8)
 SCAL_COUNT = 8
 KIND_ACTIVE, KIND_EXITED, KIND_QUEUED = 0, 1, 2
@@ -250,7 +267,8 @@ _RESTYPES = {"pz_last_error": ctypes.c_char_p, "pz_chain_free": None, "pz_set_se
              "pz_shutdown": None, "pz_state_free": None, "pz_set_small_batch_threshold": u64, "pz_comm_free": None, "pz_epoch_state_free": None,
              "pz_wire_validators_bound": u64, "pz_wire_scratch_bytes": u64,
              "pz_wire_attestations_bound": u64, "pz_wire_attestations_scratch_bytes": u64,
-             "pz_unwire_attestations_scratch_bytes": u64, "pz_unwire_blocks_scratch_bytes": u64}
+             "pz_unwire_attestations_scratch_bytes": u64, "pz_unwire_blocks_scratch_bytes": u64,
+             "pz_vote_cache_free": None, "pz_vote_cache_scratch_bytes": u64}
 SERIAL_DEFAULT = 65536        # the library's default serial threshold (bytes)
 SERIAL_ON_GPU = (1 << 64) - 1  # pz_set_serial_threshold value that keeps every message on the GPU
 

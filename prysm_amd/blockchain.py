@@ -89,6 +89,52 @@ def check_attestations(atts, block_slots, last_justified_slot, last_state_recalc
     return status[:n], ci, pstart[:n]
 
 
+def _to_device(a, dev):
+    """A numpy array as a device tensor (torch has no unsigned 32/64-bit types: they travel as
+    int32 / int64)."""
+    import torch
+
+    a = a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32) if a.dtype == np.uint32 else a
+    with warnings.catch_warnings():  # (a read-only source, e.g. np.frombuffer: it is only copied from)
+        warnings.simplefilter("ignore", UserWarning)
+        return torch.from_numpy(a).to(dev)
+
+
+def _split_decode_check(payload, offsets, last_justified_slot, last_state_recalc, n_recent, shard_and_committees,
+                        device, want_committee):
+    """The steps the ``*_serialized_blocks`` functions share, on the current stream: ``payload``
+    (the blocks' bytes, with whatever slack the caller's later kernels want) goes to the device
+    once, is split (``pz_dev_unwire_blocks``), decoded (``pz_dev_unwire_attestations``) and checked
+    (``pz_dev_check_attestations``).  Only the attestation count visits the host.  Returns the
+    device tensors: ``d_bytes``, ``d_offs``, ``blk``, ``att``, ``natt`` (an int), ``rec`` (the
+    records' decode statuses), ``status`` (the checks' statuses with ``rec`` folded in, natt rows),
+    ``committee`` (or None), ``parents_start`` and ``block_status`` (folded)."""
+    import torch
+
+    dev = torch.device("cuda", device)
+    n = len(offsets) - 1
+    d_bytes, d_offs = _to_device(payload, dev), _to_device(offsets, dev)
+    blk = wire.unwire_blocks_device(d_bytes, d_offs, n)
+    natt = int(blk["natt"].item())
+    att = wire.unwire_attestations_device(d_bytes, blk["att_beg"], blk["att_end"], natt, 0)
+    table = [_to_device(a, dev) for a in _committee_table(shard_and_committees)]
+    status = torch.zeros(max(natt, 1), dtype=torch.int32, device=dev)
+    comm = torch.zeros(max(natt, 1), dtype=torch.int32, device=dev) if want_committee else None
+    pstart = torch.zeros(max(natt, 1), dtype=torch.int64, device=dev)
+    b = _lib.AttCheckBatch(
+        natt, att["slot"].data_ptr(), att["justified_slot"].data_ptr(), att["shard_id"].data_ptr(),
+        att["n_oblique"].data_ptr(), att["attester_bitfield"].data_ptr(), att["attester_bitfield_offs"].data_ptr(),
+        blk["att_block_slot"].data_ptr(), last_justified_slot, last_state_recalc, n_recent,
+        len(shard_and_committees), *[t.data_ptr() for t in table], status.data_ptr(),
+        comm.data_ptr() if want_committee else None, pstart.data_ptr(), att["last_byte"].data_ptr())
+    lib.call("pz_dev_check_attestations", ctypes.byref(b), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    rec = att["status"][:natt]
+    status = torch.where(rec != 0, rec, status[:natt])
+    block_status = wire.folded_block_status(blk["status"], blk["att_block"][:natt], rec)
+    return {"dev": dev, "n": n, "d_bytes": d_bytes, "d_offs": d_offs, "blk": blk, "att": att, "natt": natt, "rec": rec,
+            "status": status, "committee": comm, "parents_start": pstart, "block_status": block_status}
+
+
 def check_serialized_blocks(data, offsets, last_justified_slot, last_state_recalc, n_recent, shard_and_committees,
                             device=0):
     """:func:`check_attestations` for a batch of received blocks held as bytes (block i is
@@ -103,41 +149,15 @@ def check_serialized_blocks(data, offsets, last_justified_slot, last_state_recal
     level or one of its attestations is not canonical); block i's attestations are rows
     att_first[i] .. att_first[i+1] of the other three, which are what check_attestations returns,
     except that an attestation whose record is not canonical reports PZ_EINVAL."""
-    import torch
-
-    dev = torch.device("cuda", device)
     data = np.ascontiguousarray(_lib.as_u8(data), dtype=np.uint8)
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-    n = len(offsets) - 1
-
-    def up(a):
-        a = a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32) if a.dtype == np.uint32 else a
-        with warnings.catch_warnings():  # (a read-only source, e.g. np.frombuffer: it is only copied from)
-            warnings.simplefilter("ignore", UserWarning)
-            return torch.from_numpy(a).to(dev)
-
-    d_bytes, d_offs = up(data if data.size else np.zeros(1, np.uint8)), up(offsets)
-    blk = wire.unwire_blocks_device(d_bytes, d_offs, n)
-    natt = int(blk["natt"].item())
-    att = wire.unwire_attestations_device(d_bytes, blk["att_beg"], blk["att_end"], natt, 0)
-    table = [up(a) for a in _committee_table(shard_and_committees)]
-    status = torch.zeros(max(natt, 1), dtype=torch.int32, device=dev)
-    comm = torch.zeros(max(natt, 1), dtype=torch.int32, device=dev)
-    pstart = torch.zeros(max(natt, 1), dtype=torch.int64, device=dev)
-    b = _lib.AttCheckBatch(
-        natt, att["slot"].data_ptr(), att["justified_slot"].data_ptr(), att["shard_id"].data_ptr(),
-        att["n_oblique"].data_ptr(), att["attester_bitfield"].data_ptr(), att["attester_bitfield_offs"].data_ptr(),
-        blk["att_block_slot"].data_ptr(), last_justified_slot, last_state_recalc, n_recent,
-        len(shard_and_committees), *[t.data_ptr() for t in table], status.data_ptr(), comm.data_ptr(),
-        pstart.data_ptr(), att["last_byte"].data_ptr())
-    lib.call("pz_dev_check_attestations", ctypes.byref(b), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    rec = att["status"][:natt]
-    status = torch.where(rec != 0, rec, status[:natt])
-    block_status = wire.folded_block_status(blk["status"], blk["att_block"][:natt], rec)
-    ci = comm[:natt].cpu().numpy().view(np.uint32).astype(np.int64)
+    d = _split_decode_check(data if data.size else np.zeros(1, np.uint8), offsets, last_justified_slot,
+                            last_state_recalc, n_recent, shard_and_committees, device, want_committee=True)
+    natt = d["natt"]
+    ci = d["committee"][:natt].cpu().numpy().view(np.uint32).astype(np.int64)
     ci[ci == 0xFFFFFFFF] = -1
-    return (block_status.cpu().numpy(), blk["att_first"].cpu().numpy().view(np.uint64), status.cpu().numpy(), ci,
-            pstart[:natt].cpu().numpy().view(np.uint64))
+    return (d["block_status"].cpu().numpy(), d["blk"]["att_first"].cpu().numpy().view(np.uint64),
+            d["status"].cpu().numpy(), ci, d["parents_start"][:natt].cpu().numpy().view(np.uint64))
 
 
 _MSG_COLS = ("slot", "shard_id", "shard_block_hash", "shard_block_hash_offs", "oblique_parent_hashes", "oblique_offs",
@@ -220,32 +240,13 @@ def digest_serialized_blocks(data, offsets, last_justified_slot, last_state_reca
     if len(recent) != n_recent:
         raise PzError(_lib.PZ_EINVAL, "recent_hashes holds %d hashes, n_recent is %d" % (len(recent), n_recent))
 
-    def up(a):
-        a = a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32) if a.dtype == np.uint32 else a
-        with warnings.catch_warnings():  # (a read-only source, e.g. np.frombuffer: it is only copied from)
-            warnings.simplefilter("ignore", UserWarning)
-            return torch.from_numpy(a).to(dev)
-
     # (the span hash reads whole dwords: 4 bytes of slack after the last block)
-    d_bytes = up(np.concatenate([data[:int(offsets[-1])] if n else data[:0], np.zeros(4, np.uint8)]))
-    d_offs = up(offsets)
+    d = _split_decode_check(np.concatenate([data[:int(offsets[-1])] if n else data[:0], np.zeros(4, np.uint8)]), offsets,
+                            last_justified_slot, last_state_recalc, n_recent, shard_and_committees, device,
+                            want_committee=False)
+    d_bytes, d_offs, blk, att, natt = d["d_bytes"], d["d_offs"], d["blk"], d["att"], d["natt"]
+    rec, status, pstart, block_status = d["rec"], d["status"], d["parents_start"], d["block_status"]
     sh = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    blk = wire.unwire_blocks_device(d_bytes, d_offs, n)
-    natt = int(blk["natt"].item())
-    att = wire.unwire_attestations_device(d_bytes, blk["att_beg"], blk["att_end"], natt, 0)
-    table = [up(a) for a in _committee_table(shard_and_committees)]
-    status = torch.zeros(max(natt, 1), dtype=torch.int32, device=dev)
-    pstart = torch.zeros(max(natt, 1), dtype=torch.int64, device=dev)
-    b = _lib.AttCheckBatch(
-        natt, att["slot"].data_ptr(), att["justified_slot"].data_ptr(), att["shard_id"].data_ptr(),
-        att["n_oblique"].data_ptr(), att["attester_bitfield"].data_ptr(), att["attester_bitfield_offs"].data_ptr(),
-        blk["att_block_slot"].data_ptr(), last_justified_slot, last_state_recalc, n_recent,
-        len(shard_and_committees), *[t.data_ptr() for t in table], status.data_ptr(), None, pstart.data_ptr(),
-        att["last_byte"].data_ptr())
-    lib.call("pz_dev_check_attestations", ctypes.byref(b), sh)
-    rec = att["status"][:natt]
-    status = torch.where(rec != 0, rec, status[:natt])
-    block_status = wire.folded_block_status(blk["status"], blk["att_block"][:natt], rec)
 
     block_hash = torch.empty((n, 32), dtype=torch.uint8, device=dev)
     att_hash = torch.empty((natt, 32), dtype=torch.uint8, device=dev)
@@ -257,7 +258,8 @@ def digest_serialized_blocks(data, offsets, last_justified_slot, last_state_reca
     if natt and n_recent < 64 and (status == ATT_PROCESSED).any().item():  # (an m > 0 row can pass with fewer)
         raise PzError(_lib.PZ_EINVAL, "n_recent %d < 64 with a PROCESSED attestation" % n_recent)
     if natt and n_recent >= 64:
-        msg, msg_len = attestation_messages_device(att, natt, status.contiguous(), pstart, up(recent), n_recent)
+        msg, msg_len = attestation_messages_device(att, natt, status.contiguous(), pstart, _to_device(recent, dev),
+                                                   n_recent)
     else:
         msg = torch.zeros((natt, 64), dtype=torch.uint8, device=dev)
         msg_len = torch.zeros(natt, dtype=torch.int32, device=dev)
@@ -265,6 +267,57 @@ def digest_serialized_blocks(data, offsets, last_justified_slot, last_state_reca
             "att_first": blk["att_first"].cpu().numpy().view(np.uint64), "att_status": status.cpu().numpy(),
             "hash": att_hash.cpu().numpy(), "key": key.cpu().numpy(), "msg": msg.cpu().numpy(),
             "msg_len": msg_len.cpu().numpy().view(np.uint32)}
+
+
+BLOCK_REJECTED, BLOCK_TALLIED, BLOCK_MIXED = 0, 1, 2  # tally_serialized_blocks' per-block report
+
+
+def tally_serialized_blocks(cache, data, offsets, last_justified_slot, last_state_recalc, n_recent,
+                            shard_and_committees, recent_hashes, balance, device=0):
+    """The T side of blockProcessing (blockchain/service.go:313-318: calculateBlockVoteCache over
+    a block's attestations, core.go:300-345) for a batch of received blocks held as bytes, against
+    one chain state, into ``cache`` (a ``prysm_amd.votes.DeviceVoteCache``): the same upload, split,
+    decode and checks as :func:`check_serialized_blocks`, then ``pz_dev_vote_cache_tally`` over the
+    decoded columns and the checks' outputs.  Which rows it takes is formed on the device; no
+    column visits the host in between (only the attestation count does, to size the launches).
+
+    A block is tallied iff its bytes are accepted (folded status PZ_OK), it has at least one
+    attestation, and every one of them -- so the last one too -- is PROCESSED.  The reference
+    goes on when only the LAST attestation passed (service.go:304-306) and then tallies the
+    failed ones as well, re-deriving their parents and committee: such a mixed block is left to
+    the engine, none of its rows is tallied, and it is reported.  Returns ``(block, att_first,
+    att_status)``: block[i] is BLOCK_TALLIED (1), BLOCK_REJECTED (0: bad bytes, no attestation or
+    the last one failed, as service.go:304-306) or BLOCK_MIXED (2); block i's attestations are
+    rows att_first[i] .. att_first[i+1] of att_status.  ``recent_hashes`` as in
+    :func:`digest_serialized_blocks`; ``balance``: the validators' balances (nval)."""
+    import torch
+
+    data = np.ascontiguousarray(_lib.as_u8(data), dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    recent = _recent_array(recent_hashes)
+    if len(recent) != n_recent:
+        raise PzError(_lib.PZ_EINVAL, "recent_hashes holds %d hashes, n_recent is %d" % (len(recent), n_recent))
+    d = _split_decode_check(data if data.size else np.zeros(1, np.uint8), offsets, last_justified_slot,
+                            last_state_recalc, n_recent, shard_and_committees, device, want_committee=True)
+    dev, n, natt, blk, status = d["dev"], d["n"], d["natt"], d["blk"], d["status"]
+    first = blk["att_first"]
+    count = first[1:] - first[:-1]
+    report = torch.zeros(n, dtype=torch.int64, device=dev)
+    if natt:
+        att_block = blk["att_block"][:natt].long()
+        proc = (status == ATT_PROCESSED).long()
+        nproc = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, att_block, proc)
+        last_ok = proc[(first[1:] - 1).clamp(min=0)] == 1
+        open_ = (d["block_status"] == _lib.PZ_OK) & (count > 0) & last_ok
+        report = open_.long() * (BLOCK_TALLIED + (BLOCK_MIXED - BLOCK_TALLIED) * (nproc != count).long())
+        take = (report == BLOCK_TALLIED)[att_block].to(torch.uint8)
+        members = np.ascontiguousarray([v for arr in shard_and_committees for e in arr for v in e[1]] or [0],
+                                       dtype=np.uint32)
+        coffs = _committee_table(shard_and_committees)[3]
+        cache.tally_columns(d["att"], natt, status.contiguous(), d["committee"], d["parents_start"],
+                            _to_device(recent, dev), _to_device(members, dev), _to_device(coffs, dev),
+                            _to_device(np.ascontiguousarray(balance, dtype=np.uint64), dev), take=take)
+    return (report.cpu().numpy(), first.cpu().numpy().view(np.uint64), status.cpu().numpy())
 
 
 class ChainPanic(RuntimeError):

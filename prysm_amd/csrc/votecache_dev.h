@@ -1,0 +1,112 @@
+// The pure rules of the device-resident block vote cache (votecache.hip), as host/device inlines:
+// the hash-to-slot table's cell encodings, home cell and probe step, common.BytesToHash from a
+// byte range, the oblique skip rule of calculateBlockVoteCache (blockchain/core.go:300-345) and
+// the place of a signed parent hash (getSignedParentHashes, core.go:348-360) among a call's
+// sources.  The kernels and the stand-alone CPU check (tests/votecache_san.cpp, plain g++ under
+// ASan+UBSan) compile the same text.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define PZ_HD __host__ __device__ __forceinline__
+#else
+#define PZ_HD inline
+#endif
+
+namespace pz {
+
+// ---- the table ---------------------------------------------------------------------------
+// Open addressing over u32 cells.  cells = the smallest power of two >= 2 * slot_cap, at least 2;
+// the home cell of a hash is le32(hash[0..4]) & (cells - 1); linear probing, wrapping around.
+// A cell holds kVcEmpty, a committed slot id (bit 31 clear), or a tentative claim
+// kVcTentative | source index (bit 31 set; a call's source count is below 2^31, so the largest
+// claim is 0xFFFFFFFE and never reads as kVcEmpty).
+constexpr uint32_t kVcEmpty = 0xFFFFFFFFu;
+constexpr uint32_t kVcTentative = 0x80000000u;
+constexpr uint32_t kVcNone = 0xFFFFFFFFu;  // src_slot / src_cell: none
+constexpr uint32_t kVcMaxSlotCap = 1u << 30;
+
+PZ_HD uint32_t vc_cells(uint32_t slot_cap) {
+  uint32_t c = 2;
+  while (c < 2ull * slot_cap) c <<= 1;
+  return c;
+}
+PZ_HD bool vc_is_empty(uint32_t cell) { return cell == kVcEmpty; }
+PZ_HD bool vc_is_slot(uint32_t cell) { return (cell & kVcTentative) == 0; }
+PZ_HD bool vc_is_claim(uint32_t cell) { return cell != kVcEmpty && (cell & kVcTentative) != 0; }
+PZ_HD uint32_t vc_claim(uint32_t source) { return kVcTentative | source; }
+PZ_HD uint32_t vc_claim_source(uint32_t cell) { return cell & ~kVcTentative; }
+
+struct Hash32 {
+  uint32_t w[8];  // little-endian words of the 32 bytes
+};
+
+PZ_HD uint32_t vc_home(const Hash32& h, uint32_t cells) { return h.w[0] & (cells - 1); }
+PZ_HD uint32_t vc_next(uint32_t cell, uint32_t cells) { return (cell + 1) & (cells - 1); }
+
+PZ_HD bool vc_hash_eq(const Hash32& a, const Hash32& b) {
+  uint32_t d = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) d |= a.w[k] ^ b.w[k];
+  return d == 0;
+}
+
+// The 32 bytes at p, at any alignment (byte loads: nothing outside [p, p + 32) is read).
+PZ_HD Hash32 vc_load_hash(const uint8_t* p) {
+  Hash32 h;
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    h.w[k] = (uint32_t)p[4 * k] | ((uint32_t)p[4 * k + 1] << 8) | ((uint32_t)p[4 * k + 2] << 16) |
+             ((uint32_t)p[4 * k + 3] << 24);
+  return h;
+}
+
+// common.BytesToHash of data[lo .. hi): the last 32 bytes of a longer range, a shorter one
+// right-aligned behind zeros.  Reads only bytes of the range.  (hi < lo counts as empty.)
+PZ_HD Hash32 vc_bytes_to_hash(const uint8_t* data, uint64_t lo, uint64_t hi) {
+  const uint64_t len = hi > lo ? hi - lo : 0;
+  if (len >= 32) return vc_load_hash(data + (hi - 32));
+  const uint32_t pad = 32u - (uint32_t)len;
+  Hash32 h;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t at = 4u * k + j;
+      if (at >= pad) w |= (uint32_t)data[lo + (at - pad)] << (8 * j);
+    }
+    h.w[k] = w;
+  }
+  return h;
+}
+
+// ---- calculateBlockVoteCache's rules --------------------------------------------------------
+constexpr uint32_t kVcParents = 64;  // params.CycleLength signed parent hashes per attestation
+
+// core.go:318-320 for one (parent, oblique element) pair: the parent is skipped when the RAW
+// element (elem_len bytes; elem = its bytes when elem_len == 32) equals it.  Go compares a
+// [32]byte converted to a slice with the element's slice, so only a 32-byte element can match.
+PZ_HD bool vc_skipped_by(const Hash32& parent, const Hash32& elem, uint64_t elem_len) {
+  return elem_len == 32 && vc_hash_eq(parent, elem);
+}
+
+// A row's parents stay inside recent[]: m <= 64 obliques and recent[ps .. ps + 64 - m) exists
+// (core.go:353's slice bounds, which the checks report as PZ_ERANGE).
+PZ_HD bool vc_parents_in_range(uint64_t m, uint64_t ps, uint64_t n_recent) {
+  return m <= kVcParents && ps <= n_recent && kVcParents - m <= n_recent - ps;
+}
+
+// The source index of parent r of a row (m obliques starting at element f0, parents_start ps):
+// source s < n_recent is recent[s], source n_recent + e is oblique element e, normalised.
+PZ_HD uint64_t vc_parent_source(uint32_t r, uint64_t m, uint64_t ps, uint64_t f0, uint64_t n_recent) {
+  const uint64_t nrec = kVcParents - m;
+  return r < nrec ? ps + r : n_recent + f0 + (r - nrec);
+}
+
+// The sticky error word's bits.
+constexpr uint64_t kVcErrPanic = 1;     // where Go panics (votes_dev.h tally_item raises bit 0)
+constexpr uint64_t kVcErrCapacity = 2;  // a call needed more slots (or probes) than the cache has
+
+}  // namespace pz

@@ -67,4 +67,131 @@ class VoteCache:
         self.bitmaps, self.totals = bm, tt
 
 
-__all__ = ["VoteCache", "_lib"]
+_COL_KEYS = ("oblique_parent_hashes", "oblique_offs", "oblique_first")
+
+
+class DeviceVoteCache:
+    """The block vote cache resident on one device (``pz_vote_cache``, prysm_amd/csrc/votecache.hip):
+    the map from hash to slot lives there too, so a tally takes the decoder's columns
+    (``wire.ATT_COLS`` keys) and the checks' outputs as they are -- no work list, no host hash map.
+
+    Scope, as the header states it: a tally covers the rows whose ``status`` is PZ_ATT_PROCESSED
+    (and ``take[i] != 0`` when ``take`` is given).  The reference also tallies the failed
+    attestations of a block whose last attestation passed; that is the engine's job
+    (``blockchain.tally_serialized_blocks`` reports such blocks and leaves them out).
+
+    The read side is ``VoteCache``'s: ``items()``, ``voters(h)``, ``total(h)``, ``h in cache``.  A
+    panic of the reference (PZ_EINDEX) or a call dropped for capacity (PZ_ERANGE) is sticky and
+    raised by every read; ``strict=False`` returns what the cache holds regardless."""
+
+    def __init__(self, nval, slot_cap, device=0):
+        self._h = _lib.ctypes.c_void_p()
+        lib.call("pz_vote_cache_new", nval, slot_cap, device, _lib.ctypes.byref(self._h))
+        self.nval, self.slot_cap, self.device = nval, slot_cap, device
+        self.words = (nval + 31) // 32
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            lib.dll.pz_vote_cache_free(h)
+            self._h = None
+
+    def tally_columns(self, cols, n, status, committee, parents_start, recent, members, coffs, balance, take=None,
+                      n_oblique_total=None):
+        """One tally of ``n`` rows held as torch device tensors, on the current stream
+        (``pz_dev_vote_cache_tally``; asynchronous).  ``cols``: the decoder's columns
+        (``attester_bitfield``(+``_offs``), the three oblique columns, optionally ``n_oblique``);
+        ``status`` int32, ``committee`` int32 and ``parents_start`` int64 as
+        ``pz_dev_check_attestations`` writes them; ``recent`` (k, 32) uint8, already normalised;
+        ``members`` int32 / ``coffs`` int64: the committees as CSR; ``balance`` int64 (nval);
+        ``take`` uint8 (optional).  ``n_oblique_total`` defaults to the elements ``oblique_offs``
+        has room for (an upper bound is enough: an element no row names is never read)."""
+        import torch
+
+        dev = status.device
+        one = torch.zeros(1, dtype=torch.uint8, device=dev)  # (a bytes column with no byte still needs an address)
+        cols = {k: one if k in ("attester_bitfield", "oblique_parent_hashes") and v is not None and not v.numel() else v
+                for k, v in cols.items()}
+        obl = {k: cols.get(k) for k in _COL_KEYS}
+        have_obl = all(v is not None for v in obl.values())
+        if n_oblique_total is None:
+            n_oblique_total = max(int(obl["oblique_offs"].numel()) - 1, 0) if have_obl else 0
+        n_recent = int(recent.numel()) // 32
+        p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        b = _lib.VoteColsBatch(
+            natt=n, n_oblique=p(cols.get("n_oblique")), n_oblique_total=n_oblique_total,
+            bits=cols["attester_bitfield"].data_ptr(), boffs=cols["attester_bitfield_offs"].data_ptr(),
+            status=p(status), committee=p(committee), parents_start=p(parents_start), take=p(take), recent=p(recent),
+            n_recent=n_recent, members=p(members), coffs=p(coffs), ncomm=max(int(coffs.numel()) - 1, 0), balance=p(balance),
+            **({k: v.data_ptr() for k, v in obl.items()} if have_obl else {}))
+        nbytes = int(lib.dll.pz_vote_cache_scratch_bytes(n, n_recent, n_oblique_total))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)  # (reused in stream order by the allocator)
+        lib.call("pz_dev_vote_cache_tally", self._h, _lib.ctypes.byref(b), scratch.data_ptr(),
+                 _lib.ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+
+    def tally_host(self, cols, n, status, committee, parents_start, recent, members, coffs, balance, take=None):
+        """The same tally over host arrays (numpy; ``pz_vote_cache_tally``, synchronous)."""
+        def arr(a, dt):
+            return None if a is None else np.ascontiguousarray(a, dtype=dt)
+
+        keep = {"bits": arr(cols["attester_bitfield"], np.uint8), "boffs": arr(cols["attester_bitfield_offs"], np.uint64),
+                "status": arr(status, np.int32), "committee": arr(committee, np.uint32),
+                "parents_start": arr(parents_start, np.uint64), "take": arr(take, np.uint8),
+                "recent": arr(recent, np.uint8), "members": arr(members, np.uint32), "coffs": arr(coffs, np.uint64),
+                "balance": arr(balance, np.uint64), "n_oblique": arr(cols.get("n_oblique"), np.uint64)}
+        n_oblique_total = 0
+        if all(cols.get(k) is not None for k in _COL_KEYS):
+            keep["oblique_parent_hashes"] = arr(cols["oblique_parent_hashes"], np.uint8)
+            keep["oblique_offs"] = arr(cols["oblique_offs"], np.uint64)
+            keep["oblique_first"] = arr(cols["oblique_first"], np.uint64)
+            n_oblique_total = len(keep["oblique_offs"]) - 1
+        b = _lib.VoteColsBatch(natt=n, n_oblique_total=n_oblique_total, n_recent=keep["recent"].size // 32,
+                               ncomm=len(keep["coffs"]) - 1,
+                               **{k: v.ctypes.data for k, v in keep.items() if v is not None and v.size})
+        lib.call("pz_vote_cache_tally", self._h, _lib.ctypes.byref(b))
+
+    def read(self, strict=True):
+        """``(hashes (k, 32) uint8, totals (k) uint64)`` in slot order (``pz_vote_cache_read``)."""
+        cnt = _lib.ctypes.c_uint64(0)
+        dll = lib.dll
+        rc = dll.pz_vote_cache_read(self._h, None, None, 0, _lib.ctypes.byref(cnt))
+        k = cnt.value
+        hashes = np.zeros((k, 32), dtype=np.uint8)
+        totals = np.zeros(k, dtype=np.uint64)
+        if k:
+            rc = dll.pz_vote_cache_read(self._h, hashes.ctypes.data, totals.ctypes.data, k, _lib.ctypes.byref(cnt))
+        if rc != _lib.PZ_OK and (strict or rc not in (_lib.PZ_EINDEX, _lib.PZ_ERANGE)):
+            raise _lib.PzError(rc, dll.pz_last_error().decode())
+        return hashes[:cnt.value], totals[:cnt.value]
+
+    def items(self, strict=True):
+        """``{hash: VoteTotalDeposit}``."""
+        hashes, totals = self.read(strict)
+        return {hashes[i].tobytes(): int(totals[i]) for i in range(len(totals))}
+
+    def _voters(self, h, strict):
+        words = np.zeros(self.words, dtype=np.uint32)
+        present = _lib.ctypes.c_int(0)
+        key = np.frombuffer(bytes(h), dtype=np.uint8)
+        assert key.size == 32
+        rc = lib.dll.pz_vote_cache_voters(self._h, key.ctypes.data, words.ctypes.data, _lib.ctypes.byref(present))
+        if rc != _lib.PZ_OK and (strict or rc not in (_lib.PZ_EINDEX, _lib.PZ_ERANGE)):
+            raise _lib.PzError(rc, lib.dll.pz_last_error().decode())
+        return words, bool(present.value)
+
+    def voters(self, h, strict=True):
+        """VoterIndices of ``h``, ascending (KeyError when the map has no entry)."""
+        words, present = self._voters(h, strict)
+        if not present:
+            raise KeyError(h)
+        bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:self.nval]
+        return np.nonzero(bits)[0].astype(np.uint32)
+
+    def total(self, h, strict=True):
+        return self.items(strict).get(bytes(h), 0)
+
+    def __contains__(self, h):
+        return self._voters(h, True)[1]
+
+
+__all__ = ["VoteCache", "DeviceVoteCache", "_lib"]
