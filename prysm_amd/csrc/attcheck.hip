@@ -85,61 +85,10 @@ extern "C" __global__ void __launch_bounds__(kThreads) pz_att_check_kernel(pz_at
   if (b.parents_start) b.parents_start[i] = pstart;
 }
 
-// Two attestations per lane with 16-B column loads and 8/16-B stores (every column and output
-// 16-B aligned): half the memory instructions of the one-per-lane form and full-width
-// streaming requests.
-// NT: nontemporal column loads (every column is read once): 80 -> 67 us per 4 M attestations
-// (tools/attcheck_probe.py, profiles/r02/attcheck_probe_r2o.txt).
-// (The bitfield byte stays a cached load: a 64-B line holds ~2.5 bitfields, so a nontemporal
-// byte load re-fetches it: 87 us against 67, profiles/r02/attcheck_probe_ntb_r2o.txt.)
-__device__ __forceinline__ void att_check_x2_body(const pz_att_check_batch& b) {
-  const uint64_t i = 2 * ((uint64_t)blockIdx.x * kThreads + threadIdx.x);
-  if (i >= b.natt) return;
-  if (i + 1 >= b.natt) {  // odd tail
-    int32_t st;
-    uint32_t comm;
-    uint64_t pstart;
-    check_one(b, b.slot[i], b.block_slot[i], b.justified_slot[i], b.n_oblique[i], b.shard_id[i], b.boffs[i],
-              b.boffs[i + 1], &st, &comm, &pstart, b.last_byte ? (int)b.last_byte[i] : -1);
-    b.status[i] = st;
-    if (b.committee) b.committee[i] = comm;
-    if (b.parents_start) b.parents_start[i] = pstart;
-    return;
-  }
-  auto ld2 = [](const uint64_t* p) {
-    typedef unsigned long long v2u __attribute__((ext_vector_type(2)));
-    const v2u x = __builtin_nontemporal_load(reinterpret_cast<const v2u*>(p));
-    return make_ulonglong2(x.x, x.y);
-  };
-  const ulonglong2 s = ld2(b.slot + i), bs = ld2(b.block_slot + i), js = ld2(b.justified_slot + i);
-  const ulonglong2 nob = ld2(b.n_oblique + i), sh = ld2(b.shard_id + i), bo = ld2(b.boffs + i);
-  const uint64_t bo2 = b.boffs[i + 2];
-  // the caller's last-byte column: both bytes in one 2-B load (i is even), beside the columns
-  int lb0 = -1, lb1 = -1;
-  if (b.last_byte) {
-    const uint32_t w = *reinterpret_cast<const uint16_t*>(b.last_byte + i);
-    lb0 = (int)(w & 0xFF);
-    lb1 = (int)(w >> 8);
-  }
-  int32_t st0, st1;
-  uint32_t c0, c1;
-  uint64_t p0, p1;
-  check_one(b, s.x, bs.x, js.x, nob.x, sh.x, bo.x, bo.y, &st0, &c0, &p0, lb0);
-  check_one(b, s.y, bs.y, js.y, nob.y, sh.y, bo.y, bo2, &st1, &c1, &p1, lb1);
-  *reinterpret_cast<int2*>(b.status + i) = make_int2(st0, st1);
-  if (b.committee) *reinterpret_cast<uint2*>(b.committee + i) = make_uint2(c0, c1);
-  if (b.parents_start) *reinterpret_cast<ulonglong2*>(b.parents_start + i) = make_ulonglong2(p0, p1);
-}
-
-// (Measured and dropped: default-policy column loads, 80 against 67 us; nontemporal output stores,
-// level -- profiles/r02/attcheck_probe_r2o.txt.)
-extern "C" __global__ void __launch_bounds__(kThreads) pz_att_check_x2_kernel(pz_att_check_batch b) {
-  att_check_x2_body(b);
-}
-
 // ---- round 6: persistent blocks with the committee table in LDS --------------------------------
-// The x2 kernel is latency-bound (VALU-busy 0.15, counted traffic 1.00x): after its column loads
-// every attestation walks the committee table in global memory -- arr_offs[idx], then
+// Round 5's kernel (one pair per lane, removed here: profiles/r06/attcheck_probe_r6g.txt) was
+// latency-bound (VALU-busy 0.15, counted traffic 1.00x): after its column loads
+// every attestation walked the committee table in global memory -- arr_offs[idx], then
 // arr_shard[e] entry by entry (a load per step, the exit data-dependent), arr_comm[e],
 // coffs[comm], coffs[comm + 1] -- four to eight dependent L2 round trips per lane.  Here each
 // block stages the table once into LDS as 32-bit words ({offsets | shards | committees |
@@ -157,6 +106,12 @@ struct PairLd {
   uint32_t lb;  // the two last bytes (last_byte column), else 0
 };
 
+// Two attestations per lane with 16-B column loads and 8/16-B stores (every column and output
+// 16-B aligned): half the memory instructions of the one-per-lane form and full-width
+// streaming requests.  The column loads are nontemporal (every column is read once): 80 -> 67 us
+// per 4 M attestations (profiles/r02/attcheck_probe_r2o.txt; nontemporal output stores measured
+// level there).  The bitfield byte stays a cached load: a 64-B line holds ~2.5 bitfields, so a
+// nontemporal byte load re-fetches it: 87 us against 67, profiles/r02/attcheck_probe_ntb_r2o.txt.
 __device__ __forceinline__ void load_pair(const pz_att_check_batch& b, uint64_t i, PairLd& x) {
   auto ld2 = [](const uint64_t* p) {
     typedef unsigned long long v2u __attribute__((ext_vector_type(2)));
@@ -291,10 +246,6 @@ extern "C" __global__ void __launch_bounds__(kPThreads) pz_att_check_p_kernel(pz
   }
 }
 
-#ifdef PZ_AB_BUILD
-static int g_attcheck_variant = 0;  // 1: round 5's x2 kernel (one pair per lane, the walk in global memory)
-#endif
-
 int check_args(const pz_att_check_batch* b) {
   if (!b) return fail(PZ_EINVAL, "batch is null");
   if (b->natt && (!b->slot || !b->justified_slot || !b->shard_id || !b->n_oblique || !b->boffs || !b->block_slot ||
@@ -308,16 +259,12 @@ int check_args(const pz_att_check_batch* b) {
 hipError_t launch_att_check(const pz_att_check_batch& b, hipStream_t s) {
   if (!b.natt) return hipSuccess;
   auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool x2 = al(b.slot) && al(b.block_slot) && al(b.justified_slot) && al(b.n_oblique) && al(b.shard_id) &&
+  const bool paired = al(b.slot) && al(b.block_slot) && al(b.justified_slot) && al(b.n_oblique) && al(b.shard_id) &&
                   al(b.boffs) && (reinterpret_cast<uintptr_t>(b.status) & 7) == 0 &&
                   (!b.committee || (reinterpret_cast<uintptr_t>(b.committee) & 7) == 0) &&
                   (!b.parents_start || al(b.parents_start)) &&
                   (!b.last_byte || (reinterpret_cast<uintptr_t>(b.last_byte) & 1) == 0);
-  bool persistent = x2 && b.natt >= 2;
-#ifdef PZ_AB_BUILD
-  if (g_attcheck_variant == 1) persistent = false;
-#endif
-  if (persistent) {
+  if (paired && b.natt >= 2) {  // (a single attestation has no pair: the one-per-lane kernel)
     static int cus = 0;
     if (!cus) {
       int dev = 0;
@@ -326,18 +273,9 @@ hipError_t launch_att_check(const pz_att_check_batch& b, hipStream_t s) {
         cus = 256;
     }
     const uint64_t npairs = b.natt / 2;
-    uint64_t per_cu = kPBlocksPerCU;
-#ifdef PZ_AB_BUILD
-    if (g_attcheck_variant == 2) per_cu = 2;  // (A/B: blocks per CU)
-    if (g_attcheck_variant == 3) per_cu = 1;
-#endif
     const uint64_t nb = std::max<uint64_t>(1, std::min<uint64_t>((npairs + kPThreads - 1) / kPThreads,
-                                                                 (uint64_t)cus * per_cu));
+                                                                 (uint64_t)cus * kPBlocksPerCU));
     hipLaunchKernelGGL(pz_att_check_p_kernel, dim3((uint32_t)nb), dim3(kPThreads), 0, s, b);
-  } else if (x2) {
-    const uint64_t lanes = (b.natt + 1) / 2;
-    hipLaunchKernelGGL(pz_att_check_x2_kernel, dim3((uint32_t)((lanes + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                       s, b);
   } else {
     hipLaunchKernelGGL(pz_att_check_kernel, dim3((uint32_t)((b.natt + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        s, b);
@@ -403,11 +341,3 @@ int pz_check_attestations(const pz_att_check_batch* hb) {
 }
 
 }  // extern "C"
-
-#ifdef PZ_AB_BUILD
-extern "C" int pz_debug_set_attcheck_variant(int v) {
-  const int old = pz::g_attcheck_variant;
-  pz::g_attcheck_variant = v;
-  return old;
-}
-#endif

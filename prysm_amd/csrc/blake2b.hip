@@ -409,12 +409,6 @@ pz_b2b_attmsg_kernel(const uint8_t* __restrict__ hlog, const uint32_t* __restric
 }
 
 // ---- host-side launchers (declared in blake2b_kernels.h) ---------------------------------
-#ifdef PZ_AB_BUILD
-static int g_fixed_variant = 1;  // (A/B library) 1: persistent LDS-DMA kernel (+ plain tail), 0: plain grid
-#else
-constexpr int g_fixed_variant = 1;
-#endif
-
 static int cu_count() {
   static int cached[64] = {0};
   int dev = 0;
@@ -442,7 +436,8 @@ hipError_t launch_b2b_fixed(const uint8_t* msgs, uint64_t stride, uint64_t len, 
   if (n == 0) return hipSuccess;
   const uint64_t nblocks = len == 0 ? 1 : (len + 127) / 128;
   const uint64_t nfull = n & ~63ull;
-  if (g_fixed_variant != 1 || stride < nblocks * 128 || nfull == 0)
+  // (strided inputs narrower than whole blocks, and under one full wave: the plain grid)
+  if (stride < nblocks * 128 || nfull == 0)
     return launch_plain(msgs, stride, len, n, out, out_bytes, stream);
   // persistent grid: 4 resident 256-thread workgroups per CU (122 VGPRs -> 4 waves/SIMD)
   const uint64_t groups = nfull / 64;
@@ -455,14 +450,6 @@ hipError_t launch_b2b_fixed(const uint8_t* msgs, uint64_t stride, uint64_t len, 
   if (e != hipSuccess || nfull == n) return e;
   return launch_plain(msgs + nfull * stride, stride, len, n - nfull, out + nfull * out_bytes, out_bytes, stream);
 }
-
-#ifdef PZ_AB_BUILD
-int set_fixed_variant(int v) {
-  const int old = g_fixed_variant;
-  g_fixed_variant = v;
-  return old;
-}
-#endif
 
 hipError_t launch_b2b_csr(const uint8_t* msgs, const uint64_t* offsets, uint64_t n, uint8_t* out,
                           uint32_t out_bytes, hipStream_t stream) {

@@ -507,15 +507,12 @@ struct PinVec {
 
 [[maybe_unused]] constexpr uint64_t kVoteTraceFlushes = 256, kVoteTraceWaves = 512;  // (A/B: PZ_VOTE_TRACE)
 
-// The walk's per-call switches (read_knobs), set once per pz_chain_process_blocks call: the
-// product's choices plus pz_chain_options; the A/B library (make ab, -DPZ_AB_BUILD) also reads the
-// measured-and-dropped forms from the environment there.
+// The walk's per-call switches (read_knobs), set once per pz_chain_process_blocks call from
+// pz_chain_options; the A/B library (make ab, -DPZ_AB_BUILD) also reads the tally's trace switch
+// from the environment there.
 struct Knobs {
-  int vote_path = 2;            // (A/B: PZ_VOTE_PATH; VotePath: 0 segments, 1 packed, 2 direct)
   bool vote_groups = true;      // pz_chain_options.tally_forms bit 0: the per-attestation tally
   bool vote_trace = false;      // (A/B: PZ_VOTE_TRACE, tools/vote_trace.py)
-  bool epoch_pack_direct = false;  // (A/B: PZ_EPOCH_PACK=direct)
-  bool epoch_prep_after = true;    // (A/B: PZ_EPOCH_PREP=merged: false)
 };
 
 // A recent window's parent ids as a run (votes.h VoteRec) over its positions [0, nw): shared by
@@ -541,10 +538,6 @@ enum ProfSlot {
 // every 16 / 64 / 256 attestations gave 57k / 86k / 97k blocks/s against 102k for
 // flushing only at the transitions (10,000 blocks, 65,536 validators).
 constexpr size_t kFlushAtts = 1 << 16;
-
-// The pipelined walk's producer runs at most kRing chunks of kChunk blocks ahead (Feeder).
-constexpr uint64_t kChunk = 512;
-constexpr int kRing = 4;
 
 // Staging of one digest batch (pinned host buffers and their device copies).
 struct DigestBufs {
@@ -591,7 +584,6 @@ struct RankDev {
   DevArr<uint64_t> bm;
   DevArr<uint64_t> totals;
   DevArr<uint8_t> present;
-  DevArr<uint8_t> d_qpack;
   DevArr<uint64_t> d_err;      // sticky tally panic flag
   DevArr<uint32_t> v_ticket;   // the fused gather's arrival ticket (left zero)
   DevArr<uint64_t> v_trace;    // (PZ_VOTE_TRACE, tools/ only) per flush and wave, the tally's phase stamps
@@ -604,7 +596,6 @@ struct RankDev {
   DevArr<uint32_t> e_blk, e_list, e_win;
   DevArr<uint8_t> e_pack;      // one H2D per transition: bitfields, offsets, committees, ... (sharded)
   DevArr<uint32_t> e_ticket;   // one rank: the reward pass's hand-off ticket (left zero)
-  hipEvent_t q_ev = nullptr;   // this rank's copy of the pinned tally arena is done (staged path)
   hipEvent_t vq_ev[2] = {};    // this rank's last reader of Engine::vq[i] is done
   hipEvent_t ev_epoch = nullptr, ev_t64 = nullptr;
 };
@@ -613,11 +604,9 @@ struct Engine {
   uint64_t nval = 0;
   int device = 0;
   hipStream_t s = nullptr;  // local rank 0's stream: hashing, the digest and message batches
-  hipStream_t s2 = nullptr;  // local rank 0's second stream: the pipelined digest batches
-  DigestBufs dbatch;         // the digest batch of an unpipelined call
-  DigestBufs ring[kRing];    // the pipelined calls' digest batches, reused chunk after chunk
-  hipEvent_t ring_ev[kRing] = {};
-  // the batch path's digest batch runs on s2 in two parts: the block digests (the walk waits
+  hipStream_t s2 = nullptr;  // local rank 0's second stream: the call's digest batch
+  DigestBufs dbatch;         // the call's digest batch
+  // the digest batch runs on s2 in two parts: the block digests (the walk waits
   // for ev_dblk) and the attestations' Hash / Key (results only: collected after the walk)
   hipEvent_t ev_dblk = nullptr, ev_datt = nullptr;
   pz_comm* comm = nullptr;  // null: one device, every validator
@@ -667,10 +656,6 @@ struct Engine {
     size_t natt() const { return rec.size(); }
   } vq[2];
   int vq_cur = 0;
-  // flushes run asynchronously to the walk: the queue is packed into a pinned arena and
-  // copied with one H2D per rank; the arena is reused once every rank's copy is done
-  PinBuf q_arena;
-  bool q_arena_busy = false;
   uint64_t ncomm = 0;
   std::vector<uint64_t> h_coffs;  // the committees' first member offsets (host copy)
   uint32_t bf_stride = 4;         // the vote queue's bitfield row: >= every committee's bytes, x4
@@ -954,77 +939,42 @@ static uint32_t log_hash(Engine& g, const H32& h, bool votable = true) {
   return (uint32_t)(g.hlog.size() - 1);
 }
 
-// Enqueue the pending tally items on every rank; no host wait (the pinned arena and its
-// per-rank events make the H2D asynchronous).  Balances only change in stateRecalc's epoch,
-// which each rank's stream orders after every flush, so a flush may run any time before it.
-// With `gq` (a stateRecalc's flush on one rank), the tally's last block also gathers the 64
-// justification totals into g.tot_pin (polled by their sequence word): returns true when it
-// did so (tally_gather_enqueue's work is then done).
-// One rank's stateRecalc epoch, prepared on the host (the pack in g.e_pin, the arguments) by the
-// transition's vote flush before its tally launch, whose count blocks ride in that launch
-// (pz_vote_words_count_kernel), reading the pinned pack in place: two launches less per
-// transition.  `staged` / `counted`: done (else epoch_launch_rest does them).
+// One rank's stateRecalc epoch, prepared on the host (the pack in g.e_pin, the arguments) by
+// state_recalc after the transition's vote flush; epoch_launch_rest launches it.
 struct EpochLaunch {
   EpochArgs a;
   EpochHandoff ho;
   size_t total = 0;      // pack bytes (a multiple of 16)
   bool win = false;      // crosslink winners to form
-  bool staged = false, counted = false;
-  bool ready = false;    // prepared (by the flush's hook, or by state_recalc when nothing was flushed)
 };
-using EpochPrep = std::function<EpochLaunch*()>;
 
-// How a flush reaches the device (PZ_VOTE_PATH, read per call so that one test process can
-// run every path; A/B knob):
-//   direct (product)    no copy: the tally reads the walk's pinned queue in place (one 64-B
-//                       record per attestation, votes.h VoteRec);
-//   segments            the queue arrays copied into a device pack by ONE multi-segment stage
-//                       kernel, then the tally (one launch more per flush: 1-3 % slower,
-//                       profiles/r04/replay_ab_words_r4k.txt);
-//   packed              round 3: the queue memcpy'd into one pinned arena first, one stage copy.
-enum VotePath { kVoteSegments, kVotePacked, kVoteDirect };
 static void read_knobs(Engine& g) {
   g.kn = Knobs{};
   g.kn.vote_groups = !(g.opt.tally_forms & PZ_TALLY_PER_ATTESTATION);
 #ifdef PZ_AB_BUILD
-  auto is = [](const char* name, const char* v) {
-    const char* e = std::getenv(name);
-    return e && !std::strcmp(e, v);
-  };
-  g.kn.vote_path = is("PZ_VOTE_PATH", "packed") ? kVotePacked : is("PZ_VOTE_PATH", "segments") ? kVoteSegments : kVoteDirect;
   g.kn.vote_trace = std::getenv("PZ_VOTE_TRACE") != nullptr;
-  g.kn.epoch_pack_direct = is("PZ_EPOCH_PACK", "direct");
-  g.kn.epoch_prep_after = !is("PZ_EPOCH_PREP", "merged");
 #endif
 }
 
-static bool flush_votes_enqueue(Engine& g, const VoteGatherSlots* gq = nullptr, const EpochPrep* prep = nullptr) {
+// Enqueue the pending tally items on every rank; no host wait: the tally reads the walk's pinned
+// queue in place (one 64-B record per attestation, votes.h VoteRec), and the walk goes on in the
+// other queue.  (Copying the queue into a device pack first, by one multi-segment stage kernel
+// or through a pinned arena, cost a launch more per flush and measured 1-3 % slower,
+// profiles/r04/replay_ab_words_r4k.txt; both forms were removed.)  Balances only change in
+// stateRecalc's epoch, which each rank's stream orders after every flush, so a flush may run any
+// time before it.
+// With `gq` (a stateRecalc's flush on one rank), the tally's last block also gathers the 64
+// justification totals into g.tot_pin (polled by their sequence word): returns true when it
+// did so (tally_gather_enqueue's work is then done).
+static bool flush_votes_enqueue(Engine& g, const VoteGatherSlots* gq = nullptr) {
   Engine::VoteQueue& Q = g.vq[g.vq_cur];
   if (Q.natt() == 0) return false;
   const bool gather = gq && g.world == 1;
-  const VotePath path = (VotePath)g.kn.vote_path;
-  const bool staged = path != kVoteDirect;  // a device copy of the queue
   PhaseTimer pt(g.prof[kProfFlush]);
   const uint64_t natt = Q.natt();
-  auto al = [](size_t x) { return (x + 15) & ~size_t(15); };
-  // the device pack: rec | slots | bits
-  const size_t o_rec = 0, o_slots = o_rec + natt * sizeof(VoteRec), o_bits = o_slots + al(Q.slots.size() * 4),
-               total = staged ? o_bits + al(Q.bits.size()) : 0;
-  if (path == kVotePacked) {
-    if (g.q_arena_busy) {
-      FineTimer pw(g.prof[kProfFlushWait]);
-      for (RankDev& r : g.rk) hchk(hipEventSynchronize(r.q_ev), "event sync");
-      g.q_arena_busy = false;
-    }
-    check(g.q_arena.reserve(total));
-    uint8_t* qa = g.q_arena.p;
-    std::memcpy(qa + o_rec, Q.rec.data(), natt * sizeof(VoteRec));
-    if (Q.slots.size()) std::memcpy(qa + o_slots, Q.slots.data(), Q.slots.size() * 4);
-    if (Q.bits.size()) std::memcpy(qa + o_bits, Q.bits.data(), Q.bits.size());
-  }
-  // the grouped form (votes.h VoteGroup): the walk's queue read in place, every record in the run
-  // form, each group within kVoteGroupWords id words (PZ_VOTE_GROUPS=0: A/B and test knob)
-  bool grouped = path == kVoteDirect && Q.groupable && !Q.grp.empty() && g.kn.vote_groups;
+  // the grouped form (votes.h VoteGroup): every record in the run form, each group within
+  // kVoteGroupWords id words (pz_chain_options.tally_forms bit 0 turns it off)
+  bool grouped = Q.groupable && !Q.grp.empty() && g.kn.vote_groups;
   VoteGroup groups[kVoteMaxGroups];
   uint32_t nwaves = 0, ngroups = 0;
   if (grouped) {
@@ -1063,37 +1013,6 @@ static bool flush_votes_enqueue(Engine& g, const VoteGatherSlots* gq = nullptr, 
   Q.grp.clear();
   Q.groupable = true;
   each_rank(g, [&](RankDev& r) {
-    // Growing a device buffer frees the old one, which in-flight flushes may still read:
-    // drain the stream first (rare: the buffer doubles).
-    if (total > r.d_qpack.n) {
-      hchk(hipStreamSynchronize(r.s), "sync");
-      check(r.d_qpack.alloc(std::max<uint64_t>(total, 2 * r.d_qpack.n)));
-    }
-    if (path == kVotePacked) {
-      // the pack crosses PCIe in a kernel of this stream (a copy-engine H2D costs ~13 us more on
-      // the transition's critical path: the kernel behind it waits for the engine's signal)
-      void* src = nullptr;
-      check(g.q_arena.dev(r.dev, &src));
-      hchk(launch_stage_h2d(src, r.d_qpack.p, total, r.s), "stage H2D");
-      if (!gather) {  // (gathering: the transition's totals, later in the stream, free the arena)
-        if (!r.q_ev) hchk(hipEventCreateWithFlags(&r.q_ev, hipEventDisableTiming), "event");
-        hchk(hipEventRecord(r.q_ev, r.s), "event");
-      }
-    }
-#ifdef PZ_AB_BUILD
-    else if (path == kVoteSegments) {
-      // the queue's pinned arrays straight into the pack, one launch (no host-side copy)
-      StageSegs sg;
-      sg.nseg = 0;
-      auto seg = [&](const void* src, size_t off, size_t bytes) {
-        if (bytes) sg.seg[sg.nseg++] = StageSeg{src, r.d_qpack.p + off, (bytes + 15) / 16};
-      };
-      seg(Q.rec.dev(r.dev), o_rec, natt * sizeof(VoteRec));
-      seg(Q.slots.dev(r.dev), o_slots, Q.slots.size() * 4);
-      seg(Q.bits.dev(r.dev), o_bits, Q.bits.size());
-      hchk(launch_stage_h2d_segs(sg, r.s), "stage H2D");
-    }
-#endif
     if (!r.d_err.p) {
       check(r.d_err.alloc(1));
       hchk(hipMemsetAsync(r.d_err.p, 0, 8, r.s), "memset");
@@ -1105,15 +1024,10 @@ static bool flush_votes_enqueue(Engine& g, const VoteGatherSlots* gq = nullptr, 
     VoteWordArgs v;
     std::memset(&v, 0, sizeof v);
     v.committee = r.committee.p;
-    if (staged) {
-      v.rec = reinterpret_cast<const VoteRec*>(r.d_qpack.p + o_rec);
-      v.slots = reinterpret_cast<const uint32_t*>(r.d_qpack.p + o_slots);
-      v.bits = g.bits_inline ? nullptr : r.d_qpack.p + o_bits;
-    } else {  // read in place (pinned, mapped into this rank's device)
-      v.rec = Q.rec.dev(r.dev);
-      v.slots = Q.slots.size() ? Q.slots.dev(r.dev) : nullptr;
-      v.bits = g.bits_inline ? nullptr : Q.bits.dev(r.dev);
-    }
+    // read in place (pinned, mapped into this rank's device)
+    v.rec = Q.rec.dev(r.dev);
+    v.slots = Q.slots.size() ? Q.slots.dev(r.dev) : nullptr;
+    v.bits = g.bits_inline ? nullptr : Q.bits.dev(r.dev);
     v.natt = natt;
     if (grouped) {
       v.ngroups = ngroups;
@@ -1143,13 +1057,7 @@ static bool flush_votes_enqueue(Engine& g, const VoteGatherSlots* gq = nullptr, 
       reinterpret_cast<volatile uint64_t*>(g.tot_pin.p)[kJustifySlots + 1] = 0;
     }
 #ifdef PZ_AB_BUILD
-    if (prep) {
-      // (A/B, PZ_EPOCH_PREP=merged: the transition's epoch packed before the launch) the tally
-      // with the epoch's count blocks in one launch
-      EpochLaunch* el = (*prep)();
-      hchk(launch_vote_words_count(v, el->a, r.s), "vote tally + epoch count");
-      el->counted = true;
-    } else if (g.kn.vote_trace && r.grank == 0) {
+    if (g.kn.vote_trace && r.grank == 0) {
       // (tools/vote_trace.py: the first kVoteTraceFlushes flushes' per-wave phase stamps)
       if (!r.v_trace.p) {
         check(r.v_trace.alloc((size_t)kVoteTraceFlushes * kVoteTraceWaves * 8));
@@ -1163,8 +1071,6 @@ static bool flush_votes_enqueue(Engine& g, const VoteGatherSlots* gq = nullptr, 
       ++g.vtrace_n;
       hchk(launch_vote_words_traced(v, tr, r.s), "vote tally");
     } else
-#else
-    (void)prep;
 #endif
     {
       hchk(launch_vote_words(v, r.s), "vote tally");
@@ -1174,7 +1080,6 @@ static bool flush_votes_enqueue(Engine& g, const VoteGatherSlots* gq = nullptr, 
       hchk(hipEventRecord(r.vq_ev[g.vq_cur], r.s), "event");
     }
   });
-  if (path == kVotePacked) g.q_arena_busy = !gather;
   g.gather_poll = gather;
   // the walk goes on in the other queue, once the flush before last has stopped reading it (a
   // gathering flush is waited for by tally_gather_finish before the walk goes on)
@@ -1294,8 +1199,6 @@ static void tally_gather_wait(Engine& g) {
     std::atomic_thread_fence(std::memory_order_acquire);
     if (*sq != g.gather_seq) g.prof[kProfPollFallback] += 1;  // reported, so a fallback is not silent
     if (*sq == g.gather_seq) {
-      // every rank's flush is done: its stage kernel preceded the tally
-      g.q_arena_busy = false;
       if (reinterpret_cast<const uint64_t*>(g.tot_pin.p)[kJustifySlots])
         throw Panic{"calculateBlockVoteCache: CheckBit / validator index out of range"};
       return;
@@ -1305,7 +1208,6 @@ static void tally_gather_wait(Engine& g) {
     hchk(hipStreamSynchronize(g.rk[0].s), "stream sync (vote totals)");
   else
     hchk(hipEventSynchronize(g.ev_totals), "event sync (vote totals)");
-  g.q_arena_busy = false;  // every rank's flush is behind g.ev_totals
   if (reinterpret_cast<const uint64_t*>(g.tot_pin.p)[kJustifySlots])
     throw Panic{"calculateBlockVoteCache: CheckBit / validator index out of range"};
 }
@@ -1551,11 +1453,10 @@ static void queue_vote_cache(Engine& g, uint64_t block_slot, const Att& a, AttLo
 
 // One rank: the epoch's arguments over the pack in g.e_pin (already built), its device buffers,
 // and the hand-off that returns its results.  The kernels read the pack from r.e_pack, which
-// the transition's flush stages (or epoch_launch_rest); PZ_EPOCH_PACK=direct (A/B knob) lets
-// them read the pinned pack in place instead.
+// epoch_launch_rest stages.
 static EpochLaunch epoch_prepare_args(Engine& g, CState& C, size_t na, size_t nrec, uint64_t nbits, size_t o_boffs,
                                       size_t o_rdyn, size_t o_small, size_t o_comm, size_t o_shard, size_t o_bits,
-                                      size_t total, bool in_place) {
+                                      size_t total) {
   EpochLaunch el;
   RankDev& r = g.rk[0];
   hchk(hipSetDevice(r.dev), "hipSetDevice");
@@ -1569,18 +1470,12 @@ static EpochLaunch epoch_prepare_args(Engine& g, CState& C, size_t na, size_t nr
     hchk(hipMemsetAsync(r.e_ticket.p, 0, 4, r.s), "memset");
   }
   check(g.e_pin_out.reserve((kScal + wn + 1) * 8));
-  void *hp = nullptr, *op = nullptr;
-  check(g.e_pin.dev(r.dev, &hp));
+  void* op = nullptr;
   check(g.e_pin_out.dev(r.dev, &op));
   reinterpret_cast<volatile uint64_t*>(g.e_pin_out.p)[kScal + wn] = 0;  // (pooled memory: old words)
-  const bool direct = in_place || g.kn.epoch_pack_direct;
-  uint8_t* d = static_cast<uint8_t*>(hp);
-  if (!direct) {
-    check(r.e_pack.alloc(total));
-    d = r.e_pack.p;
-  }
+  check(r.e_pack.alloc(total));
+  uint8_t* d = r.e_pack.p;
   el.total = total;
-  el.staged = direct;  // nothing to stage when the kernels read the pinned pack
   EpochArgs& a = el.a;
   std::memset(&a, 0, sizeof a);
   a.ninst = 1;
@@ -1624,22 +1519,19 @@ static EpochLaunch epoch_prepare_args(Engine& g, CState& C, size_t na, size_t nr
   }
   g.deferred.nrec = nrec;
   g.deferred.seq = el.ho.seq;
-  el.ready = true;
   return el;
 }
 
-// The launches of a prepared one-rank epoch that the flush did not take: the stage copy and the
-// count pass (if the flush did not carry them), then winners + rewards + hand-off (one launch
-// when every validator is active, else mid with the compaction, then rewards + hand-off).
+// The launches of a prepared one-rank epoch: the stage copy and the count pass, then winners +
+// rewards + hand-off (one launch when every validator is active, else mid with the compaction,
+// then rewards + hand-off).
 static void epoch_launch_rest(Engine& g, EpochLaunch& el) {
   RankDev& r = g.rk[0];
   hchk(hipSetDevice(r.dev), "hipSetDevice");
-  if (!el.staged) {
-    void* hp = nullptr;
-    check(g.e_pin.dev(r.dev, &hp));
-    hchk(launch_stage_h2d(hp, r.e_pack.p, el.total, r.s), "stage H2D (epoch)");
-  }
-  if (!el.counted) hchk(launch_epoch_count(el.a, true, true, true, r.s), "epoch count");
+  void* hp = nullptr;
+  check(g.e_pin.dev(r.dev, &hp));
+  hchk(launch_stage_h2d(hp, r.e_pack.p, el.total, r.s), "stage H2D (epoch)");
+  hchk(launch_epoch_count(el.a, true, true, true, r.s), "epoch count");
   if (g.aa) {  // no compaction: the winners run beside the rewards (one launch)
     hchk(launch_epoch_reward_handoff(el.a, el.ho, el.win, r.s), "epoch reward");
   } else {
@@ -1650,11 +1542,9 @@ static void epoch_launch_rest(Engine& g, EpochLaunch& el) {
 
 // processCrosslinks + CalculateRewards + next-cycle balance on the device: enqueued, its
 // results landing in pinned memory behind g.ev_epoch (collected by epoch_collect).
-// out (one rank): prepare only -- the pack and the arguments into *out, the kernels read the pack
-// in place (in_place) or from the stage copy; the caller launches (the flush and
-// epoch_launch_rest).
-static void epoch_enqueue(Engine& g, CState& C, const std::vector<AttP>& pending, EpochLaunch* out = nullptr,
-                          bool in_place = false, const VoteGatherSlots* q = nullptr) {
+// One rank: the pack, the arguments and the launches (epoch_launch_rest).  Sharded: `q` is the
+// transition's gather.
+static void epoch_enqueue(Engine& g, CState& C, const std::vector<AttP>& pending, const VoteGatherSlots* q = nullptr) {
   const size_t na = pending.size();
   std::vector<Crosslink>& xl = *C.xl;
   const size_t nrec = xl.size();
@@ -1691,12 +1581,8 @@ static void epoch_enqueue(Engine& g, CState& C, const std::vector<AttP>& pending
   // the previous epoch was collected (every rank's event completed), so the staging is free
   const uint64_t nred = kScal + 2 * (uint64_t)na;  // {scal, vote, total}: one all-reduce when sharded
   if (g.world == 1) {
-    EpochLaunch el =
-        epoch_prepare_args(g, C, na, nrec, nbits, o_boffs, o_rdyn, o_small, o_comm, o_shard, o_bits, total, in_place);
-    if (out)
-      *out = el;
-    else
-      epoch_launch_rest(g, el);
+    EpochLaunch el = epoch_prepare_args(g, C, na, nrec, nbits, o_boffs, o_rdyn, o_small, o_comm, o_shard, o_bits, total);
+    epoch_launch_rest(g, el);
     return;
   }
   // sharded (world > 1): the transition's ONE collective.  Every rank's xred gets
@@ -1856,20 +1742,13 @@ static void state_recalc(Engine& g, const CP& C, const AP& A, uint64_t block_slo
       if (const uint32_t* sl = g.slot_of.find(g.hlog[recent_id(g, *A, i)])) q.slot[i] = *sl;
     }
   }
-  // one rank: the epoch is prepared inside the flush (before its tally launch)
   const bool one = g.world == 1;
-  EpochLaunch el;
-  const EpochPrep prep = [&]() -> EpochLaunch* {
-    epoch_enqueue(g, *C, A->pending, &el, true);
-    return &el;
-  };
   // The tally is launched first and the epoch packed while it runs (its count pass then a
   // launch of its own): the pack's host time is off the justification loop's wait (totals_wait
-  // 3.5 -> 2.4 ms per 10,000 blocks, profiles/r04/replay_prep_ab_r4n.txt).  PZ_EPOCH_PREP=merged
-  // (A/B, read per call): pack first, the count blocks inside the tally launch.
-  const bool prep_after = g.kn.epoch_prep_after;
+  // 3.5 -> 2.4 ms per 10,000 blocks, profiles/r04/replay_prep_ab_r4n.txt; the other form, the
+  // pack first and the count blocks inside the tally launch, was removed).
   std::array<uint64_t, 4> tl{mono_ns(), 0, 0, 0};
-  const bool gathered = flush_votes_enqueue(g, &q, one && !prep_after ? &prep : nullptr);
+  const bool gathered = flush_votes_enqueue(g, &q);
   tl[1] = mono_ns();
   PhaseTimer pt(g.prof[kProfRecalc]);
   uint64_t streak = C->streak, justified = C->jslot, finalized = C->fslot;
@@ -1877,10 +1756,9 @@ static void state_recalc(Engine& g, const CP& C, const AP& A, uint64_t block_slo
   std::vector<uint64_t> tot(kCycle, 0);
   if (one) {
     if (!gathered) tally_gather_enqueue(g, q);
-    if (!el.ready) epoch_enqueue(g, *C, A->pending, &el);  // (nothing was flushed)
-    epoch_launch_rest(g, el);
+    epoch_enqueue(g, *C, A->pending);
   } else {  // the gather, the epoch and ONE all-reduce
-    epoch_enqueue(g, *C, A->pending, nullptr, false, &q);
+    epoch_enqueue(g, *C, A->pending, &q);
   }
   tl[2] = mono_ns();
   auto nc = std::make_shared<CState>();
@@ -2606,7 +2484,7 @@ static void keep_arenas(Engine& g, CallArena* cur) {
 }
 
 // Every block, on the calling thread, before anything else (the path that keeps a call
-// all-or-nothing; pz_chain_process_blocks pipelines the parse otherwise).
+// all-or-nothing; pz_chain_process_blocks parses on the worker pool and stops at a malformed block).
 static int parse_all(const uint8_t* data, const uint64_t* offs, uint64_t n, std::vector<Block>& blocks,
                      std::shared_ptr<CallArena>* keep, int threads, PinBuf* pin = nullptr) {
   std::vector<uint64_t> first;
@@ -2707,80 +2585,7 @@ static void msg_send(Engine& g) {
   g.m_busy = true;
 }
 
-// Digest messages of blocks [b0, b1) and their na attestations (a0.. in call order), laid out
-// [blocks][attestation encodings][Key() preimages] in pinned memory, then H2D, one CSR BLAKE2b
-// launch and the D2H of the 32-byte digests, all on stream s.
-// The host half: the messages into D's pinned buffers; returns their bytes (offsets in D.offs).
-static uint64_t stage_host(const std::vector<Block>& blocks, uint64_t b0, uint64_t b1, uint64_t na, DigestBufs& D) {
-  const uint64_t nb = b1 - b0, nmsg = nb + 2 * na;
-  uint64_t total = 0;
-  for (uint64_t bi = b0; bi < b1; ++bi) {
-    total += blocks[bi].len;
-    for (auto& a : blocks[bi].atts) total += a->len + 10 + a->sbh_len + 32 * a->obl.size();
-  }
-  check(D.msgs.reserve(total + 16));  // (the pipelined producer's buffers were reserved to fit)
-  check(D.offs.reserve((nmsg + 1) * 8));
-  check(D.dig.reserve(nmsg * 32 + 32));
-  uint8_t* buf = D.msgs.p;
-  uint64_t* ho = reinterpret_cast<uint64_t*>(D.offs.p);
-  uint64_t pos = 0, k = 0, ka = nb + 1, kk = nb + na + 1;
-  ho[0] = 0;
-  for (uint64_t bi = b0; bi < b1; ++bi) ho[++k] = pos += blocks[bi].len;
-  uint64_t pa = pos;
-  for (uint64_t bi = b0; bi < b1; ++bi)
-    for (auto& a : blocks[bi].atts) ho[ka++] = pa += a->len;
-  uint64_t pk = pa;
-  for (uint64_t bi = b0; bi < b1; ++bi)
-    for (auto& a : blocks[bi].atts) ho[kk++] = pk += 10 + a->sbh_len + 32 * a->obl.size();
-  uint64_t m = nb;
-  for (uint64_t bi = b0; bi < b1; ++bi) {
-    const Block& b = blocks[bi];
-    std::memcpy(buf + ho[bi - b0], b.data, b.len);
-    for (auto& ap : b.atts) {
-      const Att& a = *ap;
-      std::memcpy(buf + ho[m], a.base, a.len);
-      // Key() preimage (types/attestation.go:61-77): a 10-byte buffer holding uvarint(slot)
-      // overwritten by uvarint(shard), ShardBlockHash, each oblique hash copied into a [32]byte
-      uint8_t* q = buf + ho[m + na];
-      std::memset(q, 0, 10);
-      uint8_t v[10];
-      size_t vl = 0;
-      for (uint64_t x = a.slot; ; x >>= 7) {
-        v[vl++] = (uint8_t)(x >= 0x80 ? (x & 0x7F) | 0x80 : x);
-        if (x < 0x80) break;
-      }
-      std::memcpy(q, v, vl);
-      vl = 0;
-      for (uint64_t x = a.shard; ; x >>= 7) {
-        v[vl++] = (uint8_t)(x >= 0x80 ? (x & 0x7F) | 0x80 : x);
-        if (x < 0x80) break;
-      }
-      std::memcpy(q, v, vl);
-      std::memcpy(q + 10, a.at(a.sbh_off), a.sbh_len);
-      uint64_t kl = 10 + a.sbh_len;
-      for (auto& o : a.obl) {
-        const H32 h = copy32(a.at(o.first), o.second);
-        std::memcpy(q + kl, h.b, 32);
-        kl += 32;
-      }
-      ++m;
-    }
-  }
-  return pk;
-}
-
-// The device half: H2D, one CSR BLAKE2b launch, D2H of the 32-byte digests, on stream s.
-static void stage_launch(uint64_t nmsg, uint64_t bytes, DigestBufs& D, hipStream_t s) {
-  check(D.d_in.alloc(bytes + 16));
-  check(D.d_out.alloc(nmsg * 32));
-  check(D.d_offs.alloc(nmsg + 1));
-  hchk(hipMemcpyAsync(D.d_offs.p, D.offs.p, (nmsg + 1) * 8, hipMemcpyHostToDevice, s), "H2D offsets");
-  if (bytes) hchk(hipMemcpyAsync(D.d_in.p, D.msgs.p, bytes, hipMemcpyHostToDevice, s), "H2D msgs");
-  hchk(launch_b2b_csr(D.d_in.p, D.d_offs.p, nmsg, D.d_out.p, 32, s), "blake2b csr");
-  hchk(hipMemcpyAsync(D.dig.p, D.d_out.p, nmsg * 32, hipMemcpyDeviceToHost, s), "D2H digests");
-}
-
-// The batch path's digest batch, reading blocks and attestation encodings where they lie in
+// The call's digest batch, reading blocks and attestation encodings where they lie in
 // the call's pinned arena (one H2D of the arena, no copy of them on the host); only the Key()
 // preimages are built.  Digests [blocks][attestation Hash][Key], 32 B each, land in D.dig.
 // Two launches on s: the nb block digests, D2H'd and then ev_blk; the attestations' Hash and
@@ -2869,121 +2674,23 @@ static void stage_digests_arena(const std::vector<Block>& blocks, uint64_t nb, u
   hchk(hipEventRecord(ev_att, s), "event");
 }
 
-static void stage_digests(const std::vector<Block>& blocks, uint64_t b0, uint64_t b1, uint64_t na, DigestBufs& D,
-                          hipStream_t s) {
-  const uint64_t bytes = stage_host(blocks, b0, b1, na, D);
-  stage_launch((b1 - b0) + 2 * na, bytes, D, s);
-}
-
-// Where the walk finds its blocks and their digests (block / attestation Hash / Key, 32 B).
-// Batch: everything parsed and hashed before the walk.  Pipelined: a producer thread parses
-// chunks of kChunk blocks into the arena and enqueues each chunk's digest batch on its own
-// stream while the walk consumes the previous chunks (SURVEY.md §8 a3/a4 hashing off the walk's
-// critical path); it stays at most kRing chunks ahead.
+// Where the walk finds its blocks and their digests (block / attestation Hash / Key): everything
+// is parsed and hashed before the walk.  (A pipelined form, a producer thread parsing and hashing
+// a chunk ahead of the walk, measured slower on the 10,000-block replay -- 177-183k vs 200-229k
+// blocks/s: the producer slows the walk's own host work, profiles/r03/replay_pipeline_r3*.txt --
+// and was removed.)
 struct Feeder {
   std::vector<Block>* blocks = nullptr;
   uint64_t n = 0, natt = 0;
-  // batch
   const uint8_t* dg = nullptr;
   uint64_t dstride = 32;
-  // pipelined
-  bool piped = false;
-  struct Slot {
-    DigestBufs* d = nullptr;  // Engine::ring[j % kRing]
-    hipEvent_t ev = nullptr;  // Engine::ring_ev[j % kRing]
-    uint64_t b0 = 0, b1 = 0, a0 = 0, na = 0, bytes = 0;
-    uint64_t launched = UINT64_MAX;  // the chunk whose digest batch was launched from this slot
-  } slot[kRing];
-  hipStream_t s2 = nullptr;
-  std::atomic<uint64_t> ready{0};     // chunks parsed and their digests enqueued
-  std::atomic<uint64_t> consumed{0};  // chunks the walk has finished
-  std::atomic<uint64_t> bad{UINT64_MAX};  // first malformed block
-  std::atomic<int> rc{0};
-  std::atomic<bool> stop{false};
-  uint64_t cur = UINT64_MAX;  // the chunk the walk is in
+  uint64_t bad = UINT64_MAX;    // first malformed block (the walk covers the n blocks before it)
   hipEvent_t att_ev = nullptr;  // non-null: the attestations' Hash / Key land behind it (after the walk)
-  double wait_s = 0;
 
-  // false: block bi is not there (a malformed block at or before it ends the walk)
-  bool ensure(uint64_t bi) {
-    if (!piped) return true;
-    const uint64_t j = bi / kChunk;
-    if (j == cur) return bi < bad.load(std::memory_order_acquire);
-    if (cur != UINT64_MAX) consumed.store(cur + 1, std::memory_order_release);
-    const auto t0 = std::chrono::steady_clock::now();
-    while (ready.load(std::memory_order_acquire) <= j && !rc.load() &&
-           bad.load(std::memory_order_acquire) > bi)
-      std::this_thread::yield();
-    if (rc.load()) throw rc.load();
-    if (bi >= bad.load(std::memory_order_acquire)) return false;
-    launch(j);
-    // the next chunk's batch goes out now, so it is done when the walk gets there
-    if (ready.load(std::memory_order_acquire) > j + 1) launch(j + 1);
-    Slot& S = slot[j % kRing];
-    hchk(hipEventSynchronize(S.ev), "event sync (digests)");
-    wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    cur = j;
-    return true;
-  }
-  // Every HIP call of the pipeline is made here, on the walk's thread: HIP calls from the
-  // producer thread (its own stream) made each of the walk's tally flushes ~4x slower (runtime
-  // lock contention; profiles/r03/replay_pipeline_r3i.txt).
-  void launch(uint64_t j) {
-    Slot& S = slot[j % kRing];
-    if (S.launched == j) return;
-    S.launched = j;
-    const uint64_t nmsg = (S.b1 - S.b0) + 2 * S.na;
-    if (nmsg) stage_launch(nmsg, S.bytes, *S.d, s2);
-    hchk(hipEventRecord(S.ev, s2), "event");
-  }
-  const uint8_t* blk(uint64_t bi) const {
-    if (!piped) return dg + bi * dstride;
-    const Slot& S = slot[(bi / kChunk) % kRing];
-    return S.d->dig.p + (bi - S.b0) * 32;
-  }
-  const uint8_t* hash(uint64_t bi, uint64_t ga) const {
-    if (!piped) return dg + (n + ga) * dstride;
-    const Slot& S = slot[(bi / kChunk) % kRing];
-    return S.d->dig.p + ((S.b1 - S.b0) + (ga - S.a0)) * 32;
-  }
-  const uint8_t* key(uint64_t bi, uint64_t ga) const {
-    if (!piped) return dg + (n + natt + ga) * dstride;
-    const Slot& S = slot[(bi / kChunk) % kRing];
-    return S.d->dig.p + ((S.b1 - S.b0) + S.na + (ga - S.a0)) * 32;
-  }
+  const uint8_t* blk(uint64_t bi) const { return dg + bi * dstride; }
+  const uint8_t* hash(uint64_t ga) const { return dg + (n + ga) * dstride; }
+  const uint8_t* key(uint64_t ga) const { return dg + (n + natt + ga) * dstride; }
 };
-
-// The producer: chunk after chunk, parse into the arena and enqueue the digest batch.
-static void feed(Engine& g, Feeder& F, const uint8_t* data, const uint64_t* offs, std::shared_ptr<CallArena> ar) {
-  try {
-    uint64_t a0 = 0;
-    for (uint64_t j = 0, b0 = 0; b0 < F.n; ++j, b0 += kChunk) {
-      while (F.consumed.load(std::memory_order_acquire) + kRing <= j) {
-        if (F.stop.load()) return;
-        std::this_thread::yield();
-      }
-      Feeder::Slot& S = F.slot[j % kRing];
-      uint64_t b1 = std::min(F.n, b0 + kChunk);
-      const uint64_t good = parse_range(data, offs, b0, b1, *ar, *F.blocks, (size_t)j);
-      b1 = good;
-      uint64_t na = 0;
-      for (uint64_t bi = b0; bi < b1; ++bi) na += (*F.blocks)[bi].atts.size();
-      S.b0 = b0;
-      S.b1 = b1;
-      S.a0 = a0;
-      S.na = na;
-      a0 += na;
-      S.d = &g.ring[j % kRing];
-      S.ev = g.ring_ev[j % kRing];
-      S.bytes = b1 > b0 ? stage_host(*F.blocks, b0, b1, na, *S.d) : 0;
-      if (good < std::min(F.n, b0 + kChunk)) F.bad.store(good, std::memory_order_release);
-      F.ready.store(j + 1, std::memory_order_release);
-      if (good < std::min(F.n, b0 + kChunk)) return;
-    }
-  } catch (int rc) {
-    F.rc.store(rc ? rc : PZ_EDEVICE);
-  }
-}
 
 static void process(Engine& g, Feeder& F, pz_block_result* br, pz_att_result* ar) {
   const uint64_t n = F.n, natt = F.natt;
@@ -3017,17 +2724,12 @@ static void process(Engine& g, Feeder& F, pz_block_result* br, pz_att_result* ar
   if (g.slot_hash.size() + n >= g.cap) grow_slots(g, std::max<uint64_t>(2 * g.cap, g.slot_hash.size() + n + 64));
   msg_att.reserve(natt);
   auto t_walk = std::chrono::steady_clock::now();
-  uint64_t logged = 0;  // block digests are logged a chunk at a time, as they arrive
   for (uint64_t bi = 0; bi < n; ++bi) {
-    if (!F.ensure(bi)) break;  // a malformed block: the call ends before it (EINVAL)
-    if (bi == logged) {
-      const uint64_t e = F.piped ? std::min(n, (bi / kChunk + 1) * kChunk) : n;
-      for (; logged < e && (!F.piped || logged < F.bad.load()); ++logged) {
-        H32 h;
-        std::memcpy(h.b, F.blk(logged), 32);
-        block_id[logged] = log_hash(g, h);
-      }
-    }
+    H32 h;
+    std::memcpy(h.b, F.blk(bi), 32);
+    block_id[bi] = log_hash(g, h);
+  }
+  for (uint64_t bi = 0; bi < n; ++bi) {
     const Block& b = blocks[bi];
     pz_block_result& r = br[bi];
     std::memcpy(r.hash, F.blk(bi), 32);
@@ -3064,8 +2766,8 @@ static void process(Engine& g, Feeder& F, pz_block_result* br, pz_att_result* ar
       can_atts = true;
       x.status = PZ_ATT_PROCESSED;
       if (!F.att_ev) {
-        std::memcpy(x.hash, F.hash(bi, a0 + j), 32);
-        std::memcpy(x.key, F.key(bi, a0 + j), 32);
+        std::memcpy(x.hash, F.hash(a0 + j), 32);
+        std::memcpy(x.key, F.key(a0 + j), 32);
       }
       x.msg_len = (uint32_t)(10 + 33 * kCycle + b.atts[j]->sbh_len);
       msg_att.push_back(a0 + j);
@@ -3130,7 +2832,7 @@ static void process(Engine& g, Feeder& F, pz_block_result* br, pz_att_result* ar
     msg_drain(g);
   }
   const uint8_t* md = g.m_pin.p;
-  const bool hk = F.att_ev != nullptr;  // the processed attestations' Hash and Key too (the batch path's second part)
+  const bool hk = F.att_ev != nullptr;  // the processed attestations' Hash and Key too (the digest batch's second part)
   if (hk) hchk(hipEventSynchronize(F.att_ev), "event sync (attestation digests)");
   // 128 B per processed attestation into the caller's results: on the worker pool when large
   auto put = [&](size_t i0, size_t i1) {
@@ -3196,13 +2898,11 @@ static void destroy_chain(pz_chain* c) {
   for (RankDev& r : g.rk) {
     (void)hipSetDevice(r.dev);
     if (r.s) (void)hipStreamSynchronize(r.s);
-    for (hipEvent_t e : {r.q_ev, r.vq_ev[0], r.vq_ev[1], r.ev_epoch, r.ev_t64})
+    for (hipEvent_t e : {r.vq_ev[0], r.vq_ev[1], r.ev_epoch, r.ev_t64})
       if (e) (void)hipEventDestroy(e);
     streams.push_back({r.dev, r.s});
   }
   for (hipEvent_t e : {g.ev_totals, g.ev_dblk, g.ev_datt})
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : g.ring_ev)
     if (e) (void)hipEventDestroy(e);
   for (hipStream_t x : {g.s2, g.ms})
     if (x) {
@@ -3335,117 +3035,70 @@ int pz_chain_process_blocks(pz_chain* c, const uint8_t* blocks, const uint64_t* 
     ~Keep() { keep_arenas(g, a.get()); }
   } keep{g, arena};
   std::vector<uint8_t> dg_slow;
-  // The batch path (default): the whole call parsed, one digest batch, then the walk.  The
-  // pipelined form (a producer thread parsing a chunk ahead, PZ_CHAIN_PIPELINE=1) measured
-  // slower on the 10,000-block replay (177-183k vs 200-229k blocks/s; the producer slows the
-  // walk's own host work, profiles/r03/replay_pipeline_r3*.txt), so it is an A/B knob.  Both
-  // end the call at a malformed block with PZ_EINVAL, the blocks before it processed.
-#ifdef PZ_AB_BUILD
-  const char* pe = std::getenv("PZ_CHAIN_PIPELINE");
-  F.piped = !long_msg && n >= 2 * kChunk && pe && pe[0] == '1';
-#else
-  F.piped = false;
-#endif
-  if (!F.piped) {
-    try {
-      PhaseTimer pt(g.prof[kProfParse]);
-      arena = make_arena(offsets, n, std::move(first), (size_t)parse_threads(offsets[n] - offsets[0]), &g.arena_pin);
-      const uint64_t good = parse_parallel(blocks, offsets, n, *arena, parsed);
-      if (good < n) {  // the walk stops before the malformed block
-        F.bad.store(good);
-        F.n = good;
-        F.natt = 0;
-        for (uint64_t bi = 0; bi < good; ++bi) F.natt += parsed[bi].atts.size();
-      }
-    } catch (int rc) {
-      return rc;
+  // The whole call parsed, one digest batch, then the walk.  A malformed block ends the call
+  // with PZ_EINVAL, the blocks before it processed.
+  try {
+    PhaseTimer pt(g.prof[kProfParse]);
+    arena = make_arena(offsets, n, std::move(first), (size_t)parse_threads(offsets[n] - offsets[0]), &g.arena_pin);
+    const uint64_t good = parse_parallel(blocks, offsets, n, *arena, parsed);
+    if (good < n) {  // the walk stops before the malformed block
+      F.bad = good;
+      F.n = good;
+      F.natt = 0;
+      for (uint64_t bi = 0; bi < good; ++bi) F.natt += parsed[bi].atts.size();
     }
-    try {
-      PhaseTimer pt(g.prof[kProfHash1]);
-      if (!long_msg) {
-        if (!g.ev_dblk) hchk(hipEventCreateWithFlags(&g.ev_dblk, hipEventDisableTiming), "event");
-        if (!g.ev_datt) hchk(hipEventCreateWithFlags(&g.ev_datt, hipEventDisableTiming), "event");
-        if (F.n) {
-          stage_digests_arena(parsed, F.n, F.natt, *arena, offsets[n] - offsets[0], g.dbatch, g.s2, g.ev_dblk,
-                              g.ev_datt);
-          hchk(hipEventSynchronize(g.ev_dblk), "event sync (block digests)");
-          F.att_ev = g.ev_datt;
-        }
-        F.dg = g.dbatch.dig.p;
-        F.dstride = 32;
-      } else {  // 64-byte digests; messages at or over the threshold on host threads
-        std::string buf;
-        std::vector<uint64_t> ho{0};
-        const uint64_t ng = F.n;
-        for (uint64_t bi = 0; bi < ng; ++bi) {
-          buf.append((const char*)parsed[bi].data, parsed[bi].len);
+  } catch (int rc) {
+    return rc;
+  }
+  try {
+    PhaseTimer pt(g.prof[kProfHash1]);
+    if (!long_msg) {
+      if (!g.ev_dblk) hchk(hipEventCreateWithFlags(&g.ev_dblk, hipEventDisableTiming), "event");
+      if (!g.ev_datt) hchk(hipEventCreateWithFlags(&g.ev_datt, hipEventDisableTiming), "event");
+      if (F.n) {
+        stage_digests_arena(parsed, F.n, F.natt, *arena, offsets[n] - offsets[0], g.dbatch, g.s2, g.ev_dblk,
+                            g.ev_datt);
+        hchk(hipEventSynchronize(g.ev_dblk), "event sync (block digests)");
+        F.att_ev = g.ev_datt;
+      }
+      F.dg = g.dbatch.dig.p;
+      F.dstride = 32;
+    } else {  // 64-byte digests; messages at or over the threshold on host threads
+      std::string buf;
+      std::vector<uint64_t> ho{0};
+      const uint64_t ng = F.n;
+      for (uint64_t bi = 0; bi < ng; ++bi) {
+        buf.append((const char*)parsed[bi].data, parsed[bi].len);
+        ho.push_back(buf.size());
+      }
+      for (uint64_t bi = 0; bi < ng; ++bi)
+        for (auto& a : parsed[bi].atts) {
+          buf.append((const char*)a->base, a->len);
           ho.push_back(buf.size());
         }
-        for (uint64_t bi = 0; bi < ng; ++bi)
-          for (auto& a : parsed[bi].atts) {
-            buf.append((const char*)a->base, a->len);
-            ho.push_back(buf.size());
+      for (uint64_t bi = 0; bi < ng; ++bi)
+        for (auto& a : parsed[bi].atts) {  // Key() preimage (types/attestation.go:61-77)
+          std::string k(10, '\0'), v;
+          put_varint(v, a->slot);
+          std::memcpy(&k[0], v.data(), v.size());
+          v.clear();
+          put_varint(v, a->shard);
+          std::memcpy(&k[0], v.data(), v.size());
+          k.append((const char*)a->at(a->sbh_off), a->sbh_len);
+          for (auto& o : a->obl) {
+            const H32 h = copy32(a->at(o.first), o.second);
+            k.append((const char*)h.b, 32);
           }
-        for (uint64_t bi = 0; bi < ng; ++bi)
-          for (auto& a : parsed[bi].atts) {  // Key() preimage (types/attestation.go:61-77)
-            std::string k(10, '\0'), v;
-            put_varint(v, a->slot);
-            std::memcpy(&k[0], v.data(), v.size());
-            v.clear();
-            put_varint(v, a->shard);
-            std::memcpy(&k[0], v.data(), v.size());
-            k.append((const char*)a->at(a->sbh_off), a->sbh_len);
-            for (auto& o : a->obl) {
-              const H32 h = copy32(a->at(o.first), o.second);
-              k.append((const char*)h.b, 32);
-            }
-            buf += k;
-            ho.push_back(buf.size());
-          }
-        hash_many(g, buf, ho, dg_slow);
-        F.dg = dg_slow.data();
-        F.dstride = 64;
-      }
-    } catch (int rc) {
-      return rc;
+          buf += k;
+          ho.push_back(buf.size());
+        }
+      hash_many(g, buf, ho, dg_slow);
+      F.dg = dg_slow.data();
+      F.dstride = 64;
     }
-  } else {
-    // the parse and the digest batches run a chunk ahead of the walk on a producer thread
-    try {
-      arena = make_arena(offsets, n, std::move(first), (size_t)((n + kChunk - 1) / kChunk), &g.arena_pin);
-    } catch (int rc) {
-      return rc;
-    }
+  } catch (int rc) {
+    return rc;
   }
-  std::thread producer;
-  if (F.piped) {
-    // the ring's pinned buffers and events, sized here for the largest chunk (the producer
-    // makes no HIP call): the messages of a chunk are its blocks, their attestation encodings
-    // (spans of the blocks) and Key() preimages of at most 10 + 16x the attestation's bytes
-    uint64_t mx = 0;
-    for (uint64_t b0 = 0; b0 < n; b0 += kChunk) mx = std::max(mx, offsets[std::min(n, b0 + kChunk)] - offsets[b0]);
-    try {
-      for (int k = 0; k < kRing; ++k) {
-        check(g.ring[k].msgs.reserve(18 * mx + 10 * (mx / 8) + 16));
-        check(g.ring[k].offs.reserve((kChunk + 2 * (mx / 8) + 2) * 8));
-        check(g.ring[k].dig.reserve((kChunk + 2 * (mx / 8) + 2) * 32));
-        if (!g.ring_ev[k]) hchk(hipEventCreateWithFlags(&g.ring_ev[k], hipEventDisableTiming), "event");
-      }
-    } catch (int rc) {
-      return rc;
-    }
-    F.s2 = g.s2;
-    producer = std::thread(feed, std::ref(g), std::ref(F), blocks, offsets, arena);
-  }
-  struct Join {  // the producer is stopped and joined on every way out (it reads F and parsed)
-    Feeder& F;
-    std::thread& t;
-    ~Join() {
-      F.stop.store(true);
-      F.consumed.store(UINT64_MAX / 2);
-      if (t.joinable()) t.join();
-    }
-  } join{F, producer};
   try {
     PhaseTimer pt(g.prof[kProfProcess]);
     process(g, F, block_out, att_out);
@@ -3456,7 +3109,6 @@ int pz_chain_process_blocks(pz_chain* c, const uint8_t* blocks, const uint64_t* 
     g.poisoned = true;
     return rc;
   }
-  g.prof[kProfHash1] += F.wait_s;
   if (!g.retired.p.empty()) {  // the call's grown-out buffers, once nothing queued reads them
     try {
       each_rank(g, [](RankDev& r) {
@@ -3471,9 +3123,8 @@ int pz_chain_process_blocks(pz_chain* c, const uint8_t* blocks, const uint64_t* 
     }
     g.retired.release();
   }
-  const uint64_t bad = F.bad.load();
-  if (bad < n) return fail(PZ_EINVAL, "block %llu is not a canonical BeaconBlock encoding (blocks before it were "
-                                      "processed)", (unsigned long long)bad);
+  if (F.bad < n) return fail(PZ_EINVAL, "block %llu is not a canonical BeaconBlock encoding (blocks before it were "
+                                      "processed)", (unsigned long long)F.bad);
   return PZ_OK;
 }
 

@@ -1567,31 +1567,6 @@ hipError_t launch_epoch_count(const EpochArgs& a, bool do_val, bool do_pop, bool
   return hipGetLastError();
 }
 
-#ifdef PZ_AB_BUILD
-// A stateRecalc's vote-cache tally and its epoch's count pass in ONE launch (the chain
-// engine, one rank): blocks [0, ntb) are the voter-major tally (votes_dev.h), the rest the
-// count pass's blocks.  The two read the same pre-reward balances and write disjoint buffers; the
-// tally blocks come first, so the walk's wait (their gathered totals) is not behind the count.
-static_assert(kVoteWordThreads == kThreads, "one block shape for both parts");
-extern "C" __global__ void __launch_bounds__(kThreads)
-pz_vote_words_count_kernel(VoteWordArgs v, uint32_t ntb, EpochArgs a, CountGrid g) {
-  if (blockIdx.x < ntb)
-    vote_words_body(v, ntb, blockIdx.x);
-  else
-    count_body<0>(a, g, blockIdx.x - ntb);
-}
-
-hipError_t launch_vote_words_count(const VoteWordArgs& v, const EpochArgs& a, hipStream_t s) {
-  const CountGrid g = count_grid(a, true, true, true);
-  const uint32_t ntb = v.natt ? vote_word_blocks(v) : 0;
-  const uint64_t blocks = ntb + g.nvb + g.npb + g.nxb;
-  if (!blocks) return hipSuccess;
-  hipLaunchKernelGGL(pz_vote_words_count_kernel, dim3((uint32_t)blocks), dim3(kThreads), 0, s, v, ntb, a, g);
-  return hipGetLastError();
-}
-
-#endif
-
 hipError_t launch_epoch_winners(const EpochArgs& a, hipStream_t s) {
   const uint64_t n = (uint64_t)a.ninst * a.natt;
   if (!n) return hipSuccess;

@@ -350,8 +350,3 @@ uint32_t pz_set_host_threads(uint32_t n) { return set_host_threads(n); }
 uint64_t pz_set_small_batch_threshold(uint64_t compressions) { return set_small_batch_threshold(compressions); }
 
 }  // extern "C"
-
-#ifdef PZ_AB_BUILD
-// The A/B library only: select the fixed-length hash kernel variant for in-process A/B timing.
-extern "C" int pz_debug_set_hash_variant(int v) { return pz::set_fixed_variant(v); }
-#endif

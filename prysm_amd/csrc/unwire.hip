@@ -37,19 +37,18 @@ constexpr int kAttCols = 7;  // d_totals' order: three bytes fields, elements, e
 typedef __attribute__((address_space(1))) uint8_t gbyte;
 
 // 16-byte unaligned pieces, the last one overlapping the one before it with the same bytes:
-// every load and store lies inside [0, len) (gfx950 runs unaligned global accesses).  PIECES
-// false (the A/B library only): byte by byte.
+// every load and store lies inside [0, len) (gfx950 runs unaligned global accesses); a span under
+// 16 bytes goes byte by byte.
 __device__ __forceinline__ void copy16(gbyte* dst, const gbyte* src) {
   uint4 v;
   __builtin_memcpy(&v, src, 16);
   __builtin_memcpy(dst, &v, 16);
 }
 
-template <bool PIECES>
 __device__ __forceinline__ void copy_span(uint8_t* dst, const uint8_t* src, uint64_t len) {
   gbyte* o = reinterpret_cast<gbyte*>((uintptr_t)dst);
   const gbyte* s = reinterpret_cast<const gbyte*>((uintptr_t)src);
-  if (PIECES && len >= 16) {
+  if (len >= 16) {
     uint64_t k = 0;
     for (; k + 16 <= len; k += 16) copy16(o + k, s + k);
     if (k < len) copy16(o + len - 16, s + len - 16);
@@ -166,7 +165,7 @@ struct AttDst {
 };
 
 // The record's visitor: fields into AttRec.  W: also write the elements and the sig values.
-template <bool W, bool PIECES>
+template <bool W>
 struct AttVisit {
   const AttArgs& a;
   AttRec& r;
@@ -189,7 +188,7 @@ struct AttVisit {
   __device__ __forceinline__ bool oblique(uint64_t q, uint64_t len) {
     if (W) {
       a.o.oblique_offs[dst.el + r.nel] = dst.elb + r.elb;
-      copy_span<PIECES>(a.o.oblique_parent_hashes + dst.elb + r.elb, a.d + q, len);
+      copy_span(a.o.oblique_parent_hashes + dst.elb + r.elb, a.d + q, len);
     }
     ++r.nel;
     r.elb += len;
@@ -202,27 +201,28 @@ struct AttVisit {
   }
 };
 
-template <bool W, bool PIECES = true, bool WIN = true>
+template <bool W>
 __device__ __forceinline__ bool walk_att(const AttArgs& a, uint64_t beg, uint64_t end, AttRec& r, const AttDst& dst) {
   r = AttRec{};
   if (end < beg) return false;
-  canon::OffsetCursor<WIN> c = canon::OffsetCursor<WIN>::over(a.d, beg, end);
+  canon::OffsetCursor<true> c = canon::OffsetCursor<true>::over(a.d, beg, end);
   if (a.field) {  // the frame: that field's key and a length that covers exactly the rest
     const uint64_t k = canon::get_varint(c);
     if (!c.ok || k != (((uint64_t)a.field << 3) | 2)) return false;
     const uint64_t len = canon::get_varint(c);
     if (!c.ok || len != c.left()) return false;
   }
-  return canon::walk_attestation(c, AttVisit<W, PIECES>{a, r, dst});
+  return canon::walk_attestation(c, AttVisit<W>{a, r, dst});
 }
 
-template <bool WIN>
+// (The two kernels' bodies stay functions of their own, inlined into the kernels: written into the
+// kernels directly, the same statements compile to a different schedule.)
 __device__ __forceinline__ void att_size_body(const AttArgs& a) {
   const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
   uint64_t sz[kAttCols] = {0, 0, 0, 0, 0, 0, 0};
   if (i < a.n) {
     AttRec r;
-    const bool ok = walk_att<false, true, WIN>(a, a.begs[i], a.ends[i], r, AttDst{});
+    const bool ok = walk_att<false>(a, a.begs[i], a.ends[i], r, AttDst{});
     if (!ok) r = AttRec{};  // a record that fails contributes nothing
     a.o.slot[i] = r.v[0];
     a.o.shard_id[i] = r.v[1];
@@ -243,9 +243,8 @@ __device__ __forceinline__ void att_size_body(const AttArgs& a) {
   tile_sums<kAttCols>(sz, a.tiles, a.ntiles);
 }
 
-extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_att_size_kernel(AttArgs a) { att_size_body<true>(a); }
+extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_att_size_kernel(AttArgs a) { att_size_body(a); }
 
-template <bool PIECES, bool WIN = true>
 __device__ __forceinline__ void att_write_body(const AttArgs& a) {
   const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
   uint64_t sz[kAttCols - 1], at[kAttCols - 1];
@@ -267,25 +266,13 @@ __device__ __forceinline__ void att_write_body(const AttArgs& a) {
   if (i + 1 == a.n) a.o.oblique_offs[at[3] + sz[3]] = at[4] + sz[4];  // the element CSR's end
   if (a.o.status[i] != PZ_OK) return;
   AttRec r;
-  walk_att<true, PIECES, WIN>(a, a.begs[i], a.ends[i], r, AttDst{at[3], at[4], at[5]});
+  walk_att<true>(a, a.begs[i], a.ends[i], r, AttDst{at[3], at[4], at[5]});
   uint8_t* const dat[3] = {a.o.justified_block_hash, a.o.shard_block_hash, a.o.attester_bitfield};
 #pragma unroll
-  for (int k = 0; k < 3; ++k) copy_span<PIECES>(dat[k] + at[k], a.d + r.pos[k], r.len[k]);
+  for (int k = 0; k < 3; ++k) copy_span(dat[k] + at[k], a.d + r.pos[k], r.len[k]);
 }
 
-extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_att_write_kernel(AttArgs a) { att_write_body<true>(a); }
-#ifdef PZ_AB_BUILD
-extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_att_write_bytes_kernel(AttArgs a) {
-  att_write_body<false>(a);
-}
-extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_att_size_loads_kernel(AttArgs a) {
-  att_size_body<false>(a);
-}
-extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_att_write_loads_kernel(AttArgs a) {
-  att_write_body<true, false>(a);
-}
-int g_unwire_variant = 0;  // 1: the write kernel's copies byte by byte; 2: both walks a load per byte
-#endif
+extern "C" __global__ void __launch_bounds__(kTile) pz_unwire_att_write_kernel(AttArgs a) { att_write_body(a); }
 
 int att_out_args(const pz_attestation_cols_out* o, uint64_t n, uint32_t field_num) {
   if (!o) return fail(PZ_EINVAL, "columns are null");
@@ -315,23 +302,11 @@ hipError_t launch_unwire_att(AttArgs a, uint64_t* totals, void* scratch, hipStre
   a.ntiles = tiles_of(a.n);
   a.sizes = static_cast<uint64_t*>(scratch);
   a.tiles = a.sizes + (kAttCols - 1) * a.n;
-#ifdef PZ_AB_BUILD
-  if (g_unwire_variant == 2)
-    hipLaunchKernelGGL(pz_unwire_att_size_loads_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
-  else
-#endif
-    hipLaunchKernelGGL(pz_unwire_att_size_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
+  hipLaunchKernelGGL(pz_unwire_att_size_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(pz_unwire_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, a.tiles, a.ntiles, (uint32_t)kAttCols,
                      totals);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-#ifdef PZ_AB_BUILD
-  if (g_unwire_variant == 1 || g_unwire_variant == 2) {
-    hipLaunchKernelGGL(g_unwire_variant == 1 ? pz_unwire_att_write_bytes_kernel : pz_unwire_att_write_loads_kernel,
-                       dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
-    return hipGetLastError();
-  }
-#endif
   hipLaunchKernelGGL(pz_unwire_att_write_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
   return hipGetLastError();
 }
@@ -652,11 +627,3 @@ int pz_unwire_blocks(const uint8_t* blocks, const uint64_t* offsets, uint64_t n,
 }
 
 }  // extern "C"
-
-#ifdef PZ_AB_BUILD
-extern "C" int pz_debug_set_unwire_variant(int v) {
-  const int old = pz::g_unwire_variant;
-  pz::g_unwire_variant = v;
-  return old;
-}
-#endif

@@ -93,8 +93,8 @@ struct VoteWordArgs {
   const uint32_t* perm;  // the records' indices, group by group
   VoteGroup groups[kVoteMaxGroups];
 };
-constexpr uint32_t kVoteWordThreads = 256;    // the tally blocks beside an epoch count pass
-constexpr uint32_t kVoteWordMaxThreads = 1024;  // pz_vote_words_kernel's blocks (PZ_VOTE_WAVES per block)
+constexpr uint32_t kVoteWordThreads = 256;    // the grouped tally's blocks (4 waves)
+constexpr uint32_t kVoteWordMaxThreads = 1024;  // pz_vote_words_kernel's largest block (16 waves)
 // Blocks of the tally part of a launch (threads / 64 waves each).
 inline uint32_t vote_word_blocks(const VoteWordArgs& a, uint32_t threads = kVoteWordThreads) {
   if (a.ngroups) return a.nwaves;  // (one block of kVoteWordThreads per unit)
@@ -105,21 +105,6 @@ hipError_t launch_vote_words(const VoteWordArgs& a, hipStream_t s);
 // (tools/ only) the same with per-wave phase stamps into tr[wave][8] (null: none)
 #ifdef PZ_AB_BUILD  // the A/B library only
 hipError_t launch_vote_words_traced(const VoteWordArgs& a, uint64_t* tr, hipStream_t s);
-#endif
-// Up to 6 copies from mapped pinned memory to device memory in ONE launch (16 B per lane; the
-// sources may be read up to 15 bytes past their ends, so a source buffer's capacity must cover
-// ceil16 of its bytes).
-struct StageSeg {
-  const void* src;
-  void* dst;
-  uint64_t n16;
-};
-struct StageSegs {
-  StageSeg seg[6];
-  int nseg;
-};
-#ifdef PZ_AB_BUILD  // the A/B library only
-hipError_t launch_stage_h2d_segs(const StageSegs& g, hipStream_t s);
 #endif
 // Copy `bytes` (a multiple of 16) from mapped pinned host memory to device memory in a kernel on
 // stream s: 16 B per lane, so the bytes cross PCIe in one round trip of coalesced reads.

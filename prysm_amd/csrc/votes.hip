@@ -70,28 +70,6 @@ pz_stage_h2d_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, uint
     dst[i] = src[i];
 }
 
-#ifdef PZ_AB_BUILD
-// Several segments in one launch: block y copies segment y (grid-stride over x).
-extern "C" __global__ void __launch_bounds__(256)
-pz_stage_h2d_segs_kernel(StageSegs g) {
-  const StageSeg& sg = g.seg[blockIdx.y];
-  const uint4* __restrict__ src = static_cast<const uint4*>(sg.src);
-  uint4* __restrict__ dst = static_cast<uint4*>(sg.dst);
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < sg.n16; i += (uint64_t)gridDim.x * blockDim.x)
-    dst[i] = src[i];
-}
-
-hipError_t launch_stage_h2d_segs(const StageSegs& g, hipStream_t s) {
-  uint64_t mx = 0;
-  for (int k = 0; k < g.nseg; ++k) mx = std::max(mx, g.seg[k].n16);
-  if (!mx || !g.nseg) return hipSuccess;
-  const uint32_t blocks = (uint32_t)std::min<uint64_t>((mx + 255) / 256, 256);
-  hipLaunchKernelGGL(pz_stage_h2d_segs_kernel, dim3(blocks, (uint32_t)g.nseg), dim3(256), 0, s, g);
-  return hipGetLastError();
-}
-
-#endif
-
 hipError_t launch_stage_h2d(const void* host_mapped, void* dev, uint64_t bytes, hipStream_t s) {
   const uint64_t n16 = bytes / 16;
   if (!n16) return hipSuccess;

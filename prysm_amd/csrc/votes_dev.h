@@ -1,6 +1,5 @@
-// Device code of the vote-cache tally shared by votes.hip and epoch.hip (the block engine's
-// voter-major pass also runs inside pz_vote_words_count_kernel, beside a stateRecalc's epoch
-// count blocks).
+// Device code of the vote-cache tally (votes.hip: the per-item tally and the block engine's
+// voter-major pass) and the wave reductions that epoch.hip and epoch_window.hip share with it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -202,7 +202,7 @@ __device__ __forceinline__ void st_status(uint64_t* p, uint64_t v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Decoupled look-back by the whole workgroup: 512 threads x LB loads watch the 512*LB nearest
+// Decoupled look-back by the whole workgroup: 512 threads x kLbPer loads watch the 512*kLbPer nearest
 // predecessors at once, so one round trip usually reaches a published inclusive prefix even
 // when every resident tile started together.  Entry q*512 + t of a window (distance from the
 // tile) is thread t's q-th: each load instruction reads 64 consecutive status words (4 lines).
@@ -210,10 +210,9 @@ __device__ __forceinline__ void st_status(uint64_t* p, uint64_t v) {
 constexpr int kLbPer = 4;
 
 // First window's loads, issued early so their round trip overlaps other work.
-template <int LB>
-__device__ __forceinline__ void lookback_issue(uint64_t* status, uint64_t tile, uint64_t (&w)[LB]) {
+__device__ __forceinline__ void lookback_issue(uint64_t* status, uint64_t tile, uint64_t (&w)[kLbPer]) {
 #pragma unroll
-  for (int q = 0; q < LB; ++q) {
+  for (int q = 0; q < kLbPer; ++q) {
     const int64_t idx = (int64_t)tile - 1 - (q * kThreads + threadIdx.x);
     w[q] = idx >= 0 ? ld_status(status + idx) : kFlagP;  // before tile 0: prefix 0
   }
@@ -239,9 +238,9 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x) {
 // aggregates, whose sums fit 32 bits (a scalar-only tile encodes to at most 4,096 x 61 B and
 // a window holds at most 2,048 entries), plus the P itself.  `slots` is 8 waves x 4 u64.
 // Returns the window's contribution; *found says whether it held a P.
-template <int LB>
-__device__ __forceinline__ uint64_t lookback_window_waves(const uint64_t (&w)[LB], uint64_t* slots, bool* found,
+__device__ __forceinline__ uint64_t lookback_window_waves(const uint64_t (&w)[kLbPer], uint64_t* slots, bool* found,
                                                           uint32_t* trace_first) {
+  constexpr int LB = kLbPer;
   static_assert(LB <= 4, "per-level sums are packed two per slot");
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   uint32_t dw = 0xffffffffu, pa = 0, T[4] = {0, 0, 0, 0};
@@ -296,10 +295,13 @@ __device__ __forceinline__ uint64_t lookback_window_waves(const uint64_t (&w)[LB
   return sum;
 }
 
-template <int LB, bool kWaves = false>
-__device__ uint64_t lookback_finish(uint64_t* status, uint64_t tile, uint64_t (&w)[LB], uint64_t* lds,
+// kWaves: the window reduced by waves (one barrier: the scalar-only kernel); else by an LDS atomic
+// and a block scan (the bytes kernel, whose sums may pass 32 bits).
+template <bool kWaves = false>
+__device__ uint64_t lookback_finish(uint64_t* status, uint64_t tile, uint64_t (&w)[kLbPer], uint64_t* lds,
                                     uint32_t* lds_first, uint32_t* polls = nullptr, uint64_t* slots = nullptr,
                                     uint64_t* lbst = nullptr) {
+  constexpr int LB = kLbPer;
   constexpr uint32_t kWin = kThreads * LB;
   uint64_t prefix = 0;
   int64_t j = (int64_t)tile - 1;
@@ -326,7 +328,7 @@ __device__ uint64_t lookback_finish(uint64_t* status, uint64_t tile, uint64_t (&
     if (lbst && win == 0 && threadIdx.x == 0) lbst[0] = wall_clock64();  // (trace: the flags all seen)
     if (kWaves) {  // slots alternate by window: a wave is at most one barrier ahead
       bool found;
-      prefix += lookback_window_waves<LB>(w, slots + (win & 1) * 4 * (kThreads / 64), &found, lds_first);
+      prefix += lookback_window_waves(w, slots + (win & 1) * 4 * (kThreads / 64), &found, lds_first);
       if (lbst && win == 0 && threadIdx.x == 0) lbst[1] = wall_clock64();  // (trace: the window reduced)
       if (found) return prefix;
       j -= kWin;
@@ -367,13 +369,12 @@ __device__ uint64_t lookback_finish(uint64_t* status, uint64_t tile, uint64_t (&
 
 __device__ uint64_t lookback_block(uint64_t* status, uint64_t tile, uint64_t* lds, uint32_t* lds_first) {
   uint64_t w[kLbPer];
-  lookback_issue<kLbPer>(status, tile, w);
-  return lookback_finish<kLbPer>(status, tile, w, lds, lds_first);
+  lookback_issue(status, tile, w);
+  return lookback_finish(status, tile, w, lds, lds_first);
 }
 
 // Store stage[0..span) at out+base with 16-B stores: bytes up to the first 16-aligned
 // address, then 16-B chunks (each funnel-shifted out of five LDS words), then the tail.
-template <bool kNt = false>
 __device__ __forceinline__ void store_stage(uint8_t* out, uint64_t base, const uint32_t* stage, uint32_t span) {
   const uint8_t* st = reinterpret_cast<const uint8_t*>(stage);
   const uint32_t lead = (uint32_t)((16 - (base & 15)) & 15);
@@ -389,14 +390,7 @@ __device__ __forceinline__ void store_stage(uint8_t* out, uint64_t base, const u
     const uint4 v = sh ? make_uint4(__builtin_amdgcn_alignbyte(x[1], x[0], sh), __builtin_amdgcn_alignbyte(x[2], x[1], sh),
                                     __builtin_amdgcn_alignbyte(x[3], x[2], sh), __builtin_amdgcn_alignbyte(x[4], x[3], sh))
                        : make_uint4(x[0], x[1], x[2], x[3]);
-    if (kNt) {
-      typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-      v4u t;
-      t.x = v.x, t.y = v.y, t.z = v.z, t.w = v.w;
-      __builtin_nontemporal_store(t, reinterpret_cast<v4u*>(dst + j));
-    } else {
-      dst[j] = v;
-    }
+    dst[j] = v;
   }
   const uint32_t t0 = head + 16 * nq;
   if (t0 + threadIdx.x < span) out[base + t0 + threadIdx.x] = st[t0 + threadIdx.x];
@@ -418,7 +412,7 @@ __device__ __forceinline__ void load_sub(const WireValArgs& a, uint64_t first, S
 // Sizes of one sub-tile's records and their offsets inside the sub-tile (record order), from
 // ONE block scan: a record is at most 61 bytes and a sub-tile row p of 512 records at most
 // 31,232, so the four rows' sizes travel as four 16-bit lanes of one u64.
-template <int NC, bool kShflScan = false, int PER = kPer>
+template <int NC, int PER = kPer>
 __device__ __forceinline__ uint32_t sub_offsets(const WireValArgs& a, uint64_t first, const SRec<NC> (&r)[PER],
                                                 uint32_t (&off)[PER], uint64_t* lds) {
   static_assert(PER <= 4, "four 16-bit rows per scan");
@@ -429,7 +423,7 @@ __device__ __forceinline__ uint32_t sub_offsets(const WireValArgs& a, uint64_t f
     packed |= (uint64_t)(i < a.n ? frame_size(a, srec_body(r[p])) : 0) << (16 * p);
   }
   uint64_t e;
-  const uint64_t t = kShflScan ? block_scan(packed, &e, lds) : block_scan_packed(packed, &e, lds);
+  const uint64_t t = block_scan_packed(packed, &e, lds);
   __syncthreads();  // lds is reused by the next scan
   uint32_t row = 0;
 #pragma unroll
@@ -458,21 +452,17 @@ __device__ __forceinline__ uint32_t sub_offsets(const WireValArgs& a, uint64_t f
 // Round 2 (r2f-r2n): a coalesced look-back window without spills 175; its entries re-read
 // halfway through the build, the window reduced by waves (one barrier), DPP sub-tile scans
 // 163.5; nontemporal column loads 154.
-// V: an ablation knob for tools/wire_probe.py (0 in the product; output wrong otherwise):
-// bit 0 tile = blockIdx (no ticket), bit 1 no stage build, bit 2 no look-back, bit 3 no store,
-// bit 4 reload the values for the build instead of holding them, bit 5 (the product plus)
-// per-tile phase timestamps into a.trace (tools/wire_trace.py); bits 6/7 a look-back window of
-// 1,024 / 512 predecessors instead of 2,048, bit 8 (trace) wait for the look-back's first
-// window right after issuing it, to time its round trip, bit 9 no mid-build re-read of the
-// window's unpublished entries, bit 10 the look-back window reduced by an LDS atomic and a
-// block scan (four barriers) instead of by waves (one), bit 11 the sub-tile sizes scanned by
-// __shfl_up (ds_bpermute) instead of DPP, bit 12 column loads with the default cache policy
-// instead of nontemporal, bit 13 nontemporal output stores, bit 14 (tests) no inclusive
-// prefixes published (every look-back walks back to tile 0; exact output).
+// TR (the A/B library): per-tile phase timestamps into a.trace (tools/wire_trace.py).  NOPFX (the
+// A/B library, tests): no inclusive prefixes published, so every look-back walks back window
+// after window to tile 0 (exact output) -- a path ordinary runs rarely take.  (The ablations
+// this template once carried -- no ticket, no stage build, no look-back, no store, reloaded
+// values, smaller windows, no mid-build re-read, the block-scan window, shuffle scans, cached
+// column loads, nontemporal stores -- were removed; their numbers are in DESIGN.md §3 and
+// profiles/r02 .. r04.)
 // PER: records per thread per sub-tile (kPer in the product: 4,096-record tiles and a 64 KiB
 // stage, two tiles per CU).  Smaller PER shrinks the tile, its stage and its held values
 // (round 4 A/B: three tiles per CU at PER 3).
-template <int V, int NC, int PER = kPer>
+template <bool TR, bool NOPFX, int NC, int PER = kPer>
 __device__ __forceinline__ void wire_val_body(WireValArgs a, uint32_t nt_arg) {
   // (the tile count held in an SGPR from the start: left to the compiler, its kernel-argument
   // load was re-issued after the look-back, and a scalar-cache miss there under the streaming
@@ -485,20 +475,16 @@ __device__ __forceinline__ void wire_val_body(WireValArgs a, uint32_t nt_arg) {
   __shared__ uint64_t s_build_end, s_lbslots[2 * 4 * (kThreads / 64)], s_lbst[4];
   __shared__ __attribute__((aligned(16))) uint32_t stage[kStageBytes / 4 + 8];
   uint64_t ts[6];
-  if (V & 32) {
+  if (TR) {
     ts[0] = wall_clock64();
     if (threadIdx.x == 0) s_build_end = 0, s_polls = 0;
   }
-  if (V & 1) {
-    if (threadIdx.x == 0) s_tile = blockIdx.x;
-  } else if (threadIdx.x == 0) {
-    s_tile = atomicAdd(a.ticket, 1u);
-  }
+  if (threadIdx.x == 0) s_tile = atomicAdd(a.ticket, 1u);
   __syncthreads();
   const uint32_t tile = s_tile;
-  if (V & 32) ts[1] = wall_clock64();
+  if (TR) ts[1] = wall_clock64();
   const uint64_t tfirst = (uint64_t)tile * kTileRecs;
-  constexpr bool kHold = !(V & 16) && NC <= 3;  // 4-5 columns held would spill: reload them
+  constexpr bool kHold = NC <= 3;  // 4-5 columns held would spill: reload them
   // phase 1: sizes -> offsets inside the tile
   SRec<NC> r[kSub][PER];
   // A record's body size is recomputed for its build rather than held: 8 more live VGPRs
@@ -506,13 +492,13 @@ __device__ __forceinline__ void wire_val_body(WireValArgs a, uint32_t nt_arg) {
   uint32_t off[kSub][PER], agg = 0;
   if (kHold) {  // every sub-tile's loads in flight at once: one round trip, not kSub
 #pragma unroll
-    for (int j = 0; j < kSub; ++j) load_sub<NC, !(V & 4096), PER>(a, tfirst + (uint64_t)j * kSubRecs, r[j]);
+    for (int j = 0; j < kSub; ++j) load_sub<NC, true, PER>(a, tfirst + (uint64_t)j * kSubRecs, r[j]);
   }
 #pragma unroll
   for (int j = 0; j < kSub; ++j) {
     if (!kHold) load_sub<NC, false, PER>(a, tfirst + (uint64_t)j * kSubRecs, r[0]);
     const uint32_t sub =
-        sub_offsets<NC, (V & 2048) != 0, PER>(a, tfirst + (uint64_t)j * kSubRecs, r[kHold ? j : 0], off[j], lds);
+        sub_offsets<NC, PER>(a, tfirst + (uint64_t)j * kSubRecs, r[kHold ? j : 0], off[j], lds);
 #pragma unroll
     for (int p = 0; p < PER; ++p) off[j][p] += agg;
     agg += sub;
@@ -523,19 +509,14 @@ __device__ __forceinline__ void wire_val_body(WireValArgs a, uint32_t nt_arg) {
   // (tools/wire_trace.py: the build took 6.8 us with them in flight, 4.7 without).
   __builtin_amdgcn_s_waitcnt(0x0F70);  // gfx9 encoding: vmcnt(0), expcnt/lgkmcnt untouched
   if (threadIdx.x == 0) st_status(a.status + tile, (tile == 0 ? kFlagP : kFlagA) | agg);
-  if (V & 32) ts[2] = wall_clock64();
+  if (TR) ts[2] = wall_clock64();
   // the look-back's first round trip overlaps the stage build
-  constexpr int LB = (V & 128) ? 1 : (V & 64) ? 2 : kLbPer;  // window ablation (tools/)
+  constexpr int LB = kLbPer;
   uint64_t w[LB];
-  if (!(V & 4) && tile > 0) lookback_issue<LB>(a.status, tile, w);
-  uint64_t ts_arrive = 0;
+  if (tile > 0) lookback_issue(a.status, tile, w);
   uint32_t polls = 0;
-  if (V & 256) {  // trace: the first window's round trip alone (no overlap with the build)
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    ts_arrive = wall_clock64();
-  }
   const bool staged = agg <= kStageBytes && !a.offs;
-  if (staged && !(V & 2)) {
+  if (staged) {
     uint8_t* st = reinterpret_cast<uint8_t*>(stage);
 #pragma unroll
     for (int j = 0; j < kSub; ++j) {
@@ -550,7 +531,7 @@ __device__ __forceinline__ void wire_val_body(WireValArgs a, uint32_t nt_arg) {
       // a predecessor that started just before this tile usually publishes while the first
       // window is in flight, and the re-read's round trip now overlaps the second half of the
       // build instead of following it (tools/wire_trace.py: one re-poll per tile, ~1.2 us).
-      if (j == kSub / 2 - 1 && !(V & (512 | 4)) && tile > 0) {
+      if (j == kSub / 2 - 1 && tile > 0) {
 #pragma unroll
         for (int q = 0; q < LB; ++q) {
           const int64_t idx = (int64_t)tile - 1 - (q * kThreads + threadIdx.x);
@@ -559,22 +540,20 @@ __device__ __forceinline__ void wire_val_body(WireValArgs a, uint32_t nt_arg) {
       }
     }
   }
-  if (V & 32) {
+  if (TR) {
     ts[3] = wall_clock64();
     if ((threadIdx.x & 63) == 0) atomicMax(&s_build_end, ts[3]);
   }
   uint64_t base = 0;
-  if (V & 4) {
-    base = (uint64_t)tile * 15 * kTileRecs;  // (ablation: output wrong)
-  } else if (tile > 0) {
-    base = lookback_finish<LB, !(V & 1024)>(a.status, tile, w, lds, &s_first, (V & 32) ? &polls : nullptr, s_lbslots,
-                                            (V & 32) ? s_lbst : nullptr);
-    if ((V & 32) && threadIdx.x == 0) s_lbst[2] = wall_clock64();  // (trace: returned)
-    // (variant 16384, tests only: no inclusive prefix is published, so every look-back walks
+  if (tile > 0) {
+    base = lookback_finish<true>(a.status, tile, w, lds, &s_first, TR ? &polls : nullptr, s_lbslots,
+                                 TR ? s_lbst : nullptr);
+    if (TR && threadIdx.x == 0) s_lbst[2] = wall_clock64();  // (trace: returned)
+    // (NOPFX, tests only: no inclusive prefix is published, so every look-back walks
     // window after window back to tile 0 -- the multi-window path, with exact output)
-    if (threadIdx.x == 0 && !(V & 16384)) st_status(a.status + tile, kFlagP | (base + agg));
-    if ((V & 32) && threadIdx.x == 0) s_lbst[3] = wall_clock64();  // (trace: prefix published)
-    if (V & 32) {  // (a wave max first: an LDS atomic of a divergent value compiles to a 64-step lane loop)
+    if (threadIdx.x == 0 && !NOPFX) st_status(a.status + tile, kFlagP | (base + agg));
+    if (TR && threadIdx.x == 0) s_lbst[3] = wall_clock64();  // (trace: prefix published)
+    if (TR) {  // (a wave max first: an LDS atomic of a divergent value compiles to a 64-step lane loop)
       uint32_t m = polls;
 #pragma unroll
       for (int d = 32; d >= 1; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d, 64));
@@ -587,10 +566,10 @@ __device__ __forceinline__ void wire_val_body(WireValArgs a, uint32_t nt_arg) {
   }
   if (staged) {
     // the stage is complete: the wave-reduced look-back's barrier follows every wave's build
-    if ((V & (4 | 1024)) || tile == 0) __syncthreads();
-    if (V & 32) ts[4] = wall_clock64();
-    if (!(V & 8)) store_stage<(V & 8192) != 0>(a.out, base, stage, agg);
-    if (V & 32) {
+    if (tile == 0) __syncthreads();
+    if (TR) ts[4] = wall_clock64();
+    store_stage(a.out, base, stage, agg);
+    if (TR) {
       __syncthreads();
       ts[5] = wall_clock64();
       if (threadIdx.x == 0) {
@@ -598,7 +577,7 @@ __device__ __forceinline__ void wire_val_body(WireValArgs a, uint32_t nt_arg) {
         for (int k = 0; k < 6; ++k) t[k] = ts[k];
         t[6] = __builtin_amdgcn_s_getreg((3 << 11) | 20);  // XCC_ID
         t[7] = __builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_ID
-        t[8] = (V & 256) ? ts_arrive : s_lbst[3];  // the first poll's arrival (256) or thread 0's prefix published
+        t[8] = s_lbst[3];                    // thread 0's prefix published
         t[9] = polls;                        // re-polls by thread 0 (the nearest entries)
         t[10] = tile > 0 ? s_first : 0;      // distance of the nearest published prefix (last window)
         t[11] = s_build_end;                 // the last wave's end of the stage build
@@ -625,28 +604,23 @@ __device__ __forceinline__ void wire_val_body(WireValArgs a, uint32_t nt_arg) {
   }
 }
 
-#define PZ_WIRE_VAL_KERNEL(NAME, V, NC)                                        \
+#define PZ_WIRE_VAL_KERNEL(NAME, TR, NOPFX, NC)                                    \
   extern "C" __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) \
   NAME(WireValArgs a, uint32_t nt) {                                             \
-    wire_val_body<V, NC>(a, nt);                                                 \
+    wire_val_body<TR, NOPFX, NC>(a, nt);                                         \
   }
-PZ_WIRE_VAL_KERNEL(pz_wire_val_c0_kernel, 0, 0)
-PZ_WIRE_VAL_KERNEL(pz_wire_val_c1_kernel, 0, 1)
-PZ_WIRE_VAL_KERNEL(pz_wire_val_c2_kernel, 0, 2)
-PZ_WIRE_VAL_KERNEL(pz_wire_val_kernel, 0, 3)  // the chain's states: balance, start, end
-PZ_WIRE_VAL_KERNEL(pz_wire_val_c4_kernel, 0, 4)
-PZ_WIRE_VAL_KERNEL(pz_wire_val_c5_kernel, 0, 5)
+PZ_WIRE_VAL_KERNEL(pz_wire_val_c0_kernel, false, false, 0)
+PZ_WIRE_VAL_KERNEL(pz_wire_val_c1_kernel, false, false, 1)
+PZ_WIRE_VAL_KERNEL(pz_wire_val_c2_kernel, false, false, 2)
+PZ_WIRE_VAL_KERNEL(pz_wire_val_kernel, false, false, 3)  // the chain's states: balance, start, end
+PZ_WIRE_VAL_KERNEL(pz_wire_val_c4_kernel, false, false, 4)
+PZ_WIRE_VAL_KERNEL(pz_wire_val_c5_kernel, false, false, 5)
 #ifdef PZ_AB_BUILD
 // the A/B library only (make -C prysm_amd/csrc ab): per-tile phase stamps for tools/wire_trace.py,
 // and the multi-window look-back path for tests (no inclusive prefix published: every tile walks
 // back window after window to tile 0; exact output)
-PZ_WIRE_VAL_KERNEL(pz_wire_val_v32_kernel, 32, 3)
-PZ_WIRE_VAL_KERNEL(pz_wire_val_v16384_kernel, 16384, 3)
-// trace forms (tools/wire_trace.py): 288 the first window's round trip timed alone, 36 no
-// look-back (output wrong), 544 no mid-build re-read of the window
-PZ_WIRE_VAL_KERNEL(pz_wire_val_v288_kernel, 288, 3)
-PZ_WIRE_VAL_KERNEL(pz_wire_val_v36_kernel, 36, 3)
-PZ_WIRE_VAL_KERNEL(pz_wire_val_v544_kernel, 544, 3)
+PZ_WIRE_VAL_KERNEL(pz_wire_val_trace_kernel, true, false, 3)
+PZ_WIRE_VAL_KERNEL(pz_wire_val_noprefix_kernel, false, true, 3)
 #endif
 #undef PZ_WIRE_VAL_KERNEL
 // (Round 4 tile-geometry A/B, measured and dropped: 3,072-record tiles at 6 waves per SIMD and
@@ -752,17 +726,12 @@ hipError_t launch_wire_validators(WireValArgs a, uint64_t* scratch, hipStream_t 
     const uint32_t n32 = (uint32_t)nt;
 #ifdef PZ_AB_BUILD
     if (g_wire_variant && a.nc == 3) {
-      if (g_wire_variant == 32 || g_wire_variant == 288 || g_wire_variant == 36 || g_wire_variant == 544) {
+      if (g_wire_variant == 32) {
         if (!g_wire_trace) return hipErrorInvalidValue;
         a.trace = g_wire_trace;
-        const void* k = g_wire_variant == 288 ? (const void*)pz_wire_val_v288_kernel
-                        : g_wire_variant == 36 ? (const void*)pz_wire_val_v36_kernel
-                        : g_wire_variant == 544 ? (const void*)pz_wire_val_v544_kernel
-                                                : (const void*)pz_wire_val_v32_kernel;
-        void* args[] = {&a, const_cast<uint32_t*>(&n32)};
-        if (hipLaunchKernel(k, g, b, args, 0, s) != hipSuccess) return hipGetLastError();
+        hipLaunchKernelGGL(pz_wire_val_trace_kernel, g, b, 0, s, a, n32);
       } else if (g_wire_variant == 16384) {
-        hipLaunchKernelGGL(pz_wire_val_v16384_kernel, g, b, 0, s, a, n32);
+        hipLaunchKernelGGL(pz_wire_val_noprefix_kernel, g, b, 0, s, a, n32);
       } else {
         return hipErrorInvalidValue;
       }

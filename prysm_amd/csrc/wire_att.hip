@@ -15,8 +15,10 @@
 //   write  one 16-lane DPP row per record, four per wave: the record is assembled in an LDS
 //          stage at (offset mod 16) -- literals by the row's lanes, segments copied with aligned
 //          dword loads and written into the stage as whole dwords -- and stored in 16-B blocks.
-// Round 4 ran size, a rocPRIM inclusive scan (two launches) and the write kernel; the write
-// kernel placed segment bytes into the stage one ds_write_b8 at a time.  A one-launch form with
+// Round 4 ran size, a library inclusive scan (two launches) and the write kernel; the write
+// kernel placed segment bytes into the stage one ds_write_b8 at a time (removed; measured in
+// profiles/r05/wire_att_probe_r5*.txt, as were the other sizing tiles, the sizing loops, the
+// aligned-dword stage, the byte-loop signature varints and the nontemporal forms).  A one-launch form with
 // a look-back per wave ran 0.85 ms per 1M records against 0.41 (profiles/r05/
 // wire_att_probe_r5d.txt): ~6,000 waves are in flight, so a wave's look-back walks back over
 // many windows before it meets a published prefix; dropped.
@@ -25,9 +27,6 @@
 #include <algorithm>
 #include <mutex>
 #include <vector>
-#ifdef PZ_AB_BUILD
-#include <rocprim/device/device_scan.hpp>
-#endif
 
 #include "proto3_canon.h"  // put_varint
 #include "runtime.h"
@@ -48,7 +47,7 @@ struct AttArgs {
   const uint64_t* sfirst;  // record i owns values sfirst[i] .. sfirst[i+1]
   uint64_t n;
   uint32_t field, tag_len;
-  uint64_t* sizes;
+  uint64_t* sizes;  // (unused: round 4's size column; kept so the kernels' argument layout stands)
   uint64_t* offs;  // n+1
   uint8_t* out;
   uint64_t* status;  // [tiles] look-back status words, zero at launch
@@ -129,7 +128,8 @@ struct Head {  // the record's scalar part, the same on every lane
   uint64_t o0, o1, s0, s1;
 };
 
-[[maybe_unused]] __device__ __forceinline__ void load_head(const AttArgs& a, uint64_t i, Head& h) {
+// (the sizing's fallback for records with many elements or values, record_size)
+__device__ __forceinline__ void load_head(const AttArgs& a, uint64_t i, Head& h) {
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     h.v[k] = a.col[k] ? a.col[k][i] : 0;
@@ -279,7 +279,7 @@ __device__ __forceinline__ void write_record(const AttArgs& a, const Head& h, ui
 //    trip at a time.
 // (A persistent, software-pipelined variant that prefetched the next record's head needed
 // 130+ VGPRs -- 3 waves per SIMD -- and was slower.)
-constexpr uint32_t kStage = 768, kStageAlloc = kStage + 32, kSegMax = 64, kSegWords = kSegMax / 4 + 1;
+constexpr uint32_t kStage = 768, kStageAlloc = kStage + 32, kSegMax = 64;
 
 // A record per DPP row: 16 lanes, four records per wave.
 constexpr int kRow = 16, kRecs = 64 / kRow, kMaxOblique = kRow - 3;
@@ -287,10 +287,9 @@ constexpr int kRow = 16, kRecs = 64 / kRow, kMaxOblique = kRow - 3;
 // Sub-lane k of the row loads head word k:
 //   0-2   slot, shard_id, justified_slot
 //   3-8   bytes fields 4-6: start, end (boff[k][i], boff[k][i+1])
-//   9-10  oblique element range     11-12  signature value range     (AB form: 13-14 offs[i], offs[i+1])
+//   9-10  oblique element range     11-12  signature value range     13-14 offs[i], offs[i+1]
 constexpr int kHeadWords = 13;
 
-template <bool NTL = false>
 __device__ __forceinline__ uint64_t head_word(const AttArgs& a, int k, uint64_t i) {
   const uint64_t* p = nullptr;
   uint32_t d = 0;
@@ -303,7 +302,7 @@ __device__ __forceinline__ uint64_t head_word(const AttArgs& a, int k, uint64_t 
     p = k < 11 ? a.ofirst : k < 13 ? a.sfirst : a.offs;
     d = (k - 9) & 1;
   }
-  return p ? (NTL ? __builtin_nontemporal_load(p + i + d) : p[i + d]) : 0;
+  return p ? p[i + d] : 0;
 }
 
 __device__ __forceinline__ uint64_t rl64(uint64_t x, int k) {
@@ -340,64 +339,14 @@ __device__ __forceinline__ uint32_t rscan32(uint32_t x) {
   return x;
 }
 
-// Segment modes (the write kernel's template argument M): 0 round 4's form, the segment placed
-// in the stage byte by byte; 1 the aligned form of early round 5, stage dwords realigned with
-// v_alignbyte, the two edge words written byte-wise; 2 (the product) unaligned pieces, below.
-// 0 and 1 are kept in the A/B library only.
+// A segment (a bytes field or an oblique element) into the stage.  Round 4 placed it byte by
+// byte, early round 5 as stage dwords realigned with v_alignbyte, the two edge words written
+// byte-wise (~130 VALU instructions per segment); both were removed for the form below.
 //
-// Aligned form: the source dwords wv (aligned on the source, first byte at r), len bytes, to
-// stage bytes [d0, d0 + len).
-template <int M>
-__device__ __forceinline__ void stage_segment_aligned(uint8_t* row, uint32_t d0, uint32_t (&wv)[kSegWords + 1],
-                                                      uint32_t r, uint32_t len) {
-  if (M == 0) {
-#pragma unroll
-    for (int k = 0; k < (int)kSegWords; ++k) {
-      const uint32_t d = __builtin_amdgcn_alignbyte(wv[k + 1], wv[k], r);
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-        if ((uint32_t)(4 * k + b) < len) row[d0 + 4 * k + b] = (uint8_t)(d >> (8 * b));
-    }
-    return;
-  }
-  if (!len) return;
-  // stage word k of the segment holds source bytes r + 4k - dm .. +3 (dm = d0 mod 4): one
-  // v_alignbyte of the loaded words, one word lower when r < dm.  Words [kf, kl) are the
-  // segment's alone and go out as dwords; the first and the last word, when shared with a
-  // neighbour, are written byte by byte after the loop
-  const uint32_t dend = d0 + len, dm = d0 & 3;
-  const bool back = r < dm;
-  const uint32_t delta = (r - dm) & 3, nwo = (dm + len + 3) >> 2;
-  const uint32_t kf = (dm == 0 && len >= 4) ? 0u : 1u, kl = (dend & 3) ? nwo - 1 : nwo;
-  const uint32_t nfull = kl > kf ? kl - kf : 0u;  // (a segment inside one word has none)
-  uint32_t* sw = reinterpret_cast<uint32_t*>(row) + (d0 >> 2);
-  const uint32_t bw = d0 & ~3u;
-  uint32_t xf = 0, xl = 0;
-#pragma unroll
-  for (int k = 0; k < (int)kSegWords; ++k) {
-    const uint32_t lo = back ? (k ? wv[k - 1] : 0u) : wv[k], hi = back ? wv[k] : wv[k + 1];
-    const uint32_t x = __builtin_amdgcn_alignbyte(hi, lo, delta);
-    if (k == 0) xf = x;
-    xl = (uint32_t)k + 1 == nwo ? x : xl;
-    if ((uint32_t)k - kf < nfull) sw[k] = x;  // (k in [kf, kl); unsigned: k < kf wraps high)
-  }
-  if (kf) {
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-      if (bw + b >= d0 && bw + b < dend) row[bw + b] = (uint8_t)(xf >> (8 * b));
-  }
-  if ((dend & 3) && nwo > 1) {
-    const uint32_t lw = bw + 4 * (nwo - 1);
-#pragma unroll
-    for (int b = 0; b < 3; ++b)
-      if (lw + b < dend) row[lw + b] = (uint8_t)(xl >> (8 * b));
-  }
-}
-
-// Unaligned form: a segment of len >= 16 bytes is four 16-byte pieces at min(16c, len - 16):
+// A segment of len >= 16 bytes is four 16-byte pieces at min(16c, len - 16):
 // every load and every stage write lies inside the segment -- the last piece overlaps the one
 // before it with the same bytes -- so the neighbours' bytes are never touched and no select
-// picks a word: ~25 VALU instructions per segment against ~130 for the aligned form.  (gfx950
+// picks a word: ~25 VALU instructions per segment.  (gfx950
 // runs unaligned global and LDS accesses; HSA sets the unaligned mode.)  A segment under 16
 // bytes (none in the bench's records) is loaded at stage time as aligned words and written
 // byte by byte.
@@ -446,16 +395,13 @@ __device__ __forceinline__ void stage_segment_unaligned(uint8_t* d, const uint8_
   }
 }
 
-// NTF (A/B): bit 0 the whole 16-B output blocks stored nontemporally, bit 1 the head words
-// loaded nontemporally
-template <int M, int NTF = 0>
 __device__ __forceinline__ void wire_att_write_rows(const AttArgs& a, uint8_t (*stage)[kStageAlloc], uint64_t i0) {
   const int lane = threadIdx.x & 63;
   const int sl = lane & (kRow - 1), ri = lane / kRow;
   if (i0 >= a.n) return;
   const uint64_t i = i0 + ri;
   const bool valid = i < a.n;
-  const uint64_t hv = valid && sl < kHeadWords + 2 ? head_word<(NTF & 2) != 0>(a, sl, i) : 0;
+  const uint64_t hv = valid && sl < kHeadWords + 2 ? head_word(a, sl, i) : 0;
   // Each lane's word below it (row_shr:1) and the difference: lanes 4, 6, 8 hold bl[0..2],
   // lane 10 the oblique count, 12 the value count, 14 the size.  Only what every lane needs is
   // broadcast; a lane's own operands come by one shift or one ds_bpermute.  Counts and lengths
@@ -500,19 +446,9 @@ __device__ __forceinline__ void wire_att_write_rows(const AttArgs& a, uint8_t (*
   const uint32_t ssz = fast && (uint32_t)sl < nsig ? vlen(sv) : 0;
   const uint32_t einc = rscan32(esz), sinc = rscan32(ssz);
   const uint32_t obl = bc32<15>(einc), sigb = bc32<15>(sinc);
-  typedef const __attribute__((address_space(1))) uint32_t gword;
   const uint32_t len = fast ? (uint32_t)seg_len : 0;
-  const uint32_t r = (uint32_t)(uintptr_t)seg_src & 3;
-  uint32_t wv[kSegWords + 1];
   SegPieces sp;
-  if (M < 2) {
-    gword* ws = reinterpret_cast<gword*>((uintptr_t)seg_src & ~(uintptr_t)3);
-    const uint32_t nw = len ? (r + len + 3) / 4 : 0;
-#pragma unroll
-    for (int k = 0; k <= (int)kSegWords; ++k) wv[k] = (uint32_t)k < nw ? ws[k] : 0;
-  } else {
-    load_segment_unaligned(seg_src, len, sp);
-  }
+  load_segment_unaligned(seg_src, len, sp);
   const uint32_t sh = (uint32_t)o & 15;
   uint8_t* st = stage[ri] + sh;
   uint32_t seg_dst = 0;
@@ -553,19 +489,9 @@ __device__ __forceinline__ void wire_att_write_rows(const AttArgs& a, uint8_t (*
     const uint32_t ed = shr3(ep + 1 + vlen32(el));
     if (sl >= 3 && (uint32_t)(sl - 3) < nob) seg_dst = ed;
     const uint32_t sp = bc32<8>(pos) + 1 + vlen32(sigb);
-    if ((uint32_t)sl < nsig) {
-      if (M == 2) {
-        put_varint_pieces(st + sp + sinc - ssz, sv);
-      } else {
-        put_varint(st + sp + sinc - ssz, sv);
-      }
-    }
+    if ((uint32_t)sl < nsig) put_varint_pieces(st + sp + sinc - ssz, sv);
   }
-  if (M < 2) {
-    stage_segment_aligned<M>(stage[ri], sh + seg_dst, wv, r, len);
-  } else {
-    stage_segment_unaligned(stage[ri] + sh + seg_dst, seg_src, len, sp);
-  }
+  stage_segment_unaligned(stage[ri] + sh + seg_dst, seg_src, len, sp);
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   const uint32_t sz = fast ? (uint32_t)size : 0;
@@ -575,14 +501,7 @@ __device__ __forceinline__ void wire_att_write_rows(const AttArgs& a, uint8_t (*
   for (uint32_t q = sl; q < nblk; q += kRow) {
     const uint32_t lo = 16 * q, hi = lo + 16;
     if (lo >= sh && hi <= sh + sz) {
-      if (NTF & 1) {
-        typedef unsigned int v4u_ __attribute__((ext_vector_type(4)));
-        __builtin_nontemporal_store(*reinterpret_cast<const v4u_*>(sb + lo), reinterpret_cast<v4u_*>(ob + lo));
-      } else {
-        *reinterpret_cast<uint4*>(ob + lo) = *reinterpret_cast<const uint4*>(sb + lo);
-      }
-    } else if (M < 2) {
-      for (uint32_t x = max(lo, sh); x < min(hi, sh + sz); ++x) ob[x] = sb[x];
+      *reinterpret_cast<uint4*>(ob + lo) = *reinterpret_cast<const uint4*>(sb + lo);
     } else {  // an edge block shared with a neighbour: 1-, 2-, 4- and 8-byte pieces of [x, e)
       uint32_t x = max(lo, sh);
       const uint32_t l = min(hi, sh + sz) - x;
@@ -647,7 +566,7 @@ __device__ __forceinline__ void st_status(uint64_t* p, uint64_t v) {
 // ticket taken at start, so every predecessor of a waiting tile is running or done (the
 // dispatch order of workgroups is not guaranteed); a tile's look-back reads 1,024
 // predecessors' status words a round.
-constexpr int kSizeThreads = 512, kSizePer = 8;  // (the product's geometry; the A/B library's others below)
+constexpr int kSizeThreads = 512, kSizePer = 8;
 constexpr uint32_t kSizeTile = kSizeThreads * kSizePer;
 
 __device__ __forceinline__ uint64_t record_size(const AttArgs& a, uint64_t i) {
@@ -670,7 +589,7 @@ __device__ __forceinline__ uint64_t record_size(const AttArgs& a, uint64_t i) {
   return a.field ? a.tag_len + vlen(body) + body : body;
 }
 
-// A thread's P records sized with their loads in flight together.  Round 5's first sizing ran
+// A thread's P records sized with their loads in flight together.  Round 5's first sizing (removed) ran
 // each record's element and value loops in turn (a loop's trip count is data, so nothing of
 // record q + 1 was issued before record q's loops ended): ~5 dependent round trips per record,
 // 40 per thread.  Here the heads of all P records load first; then, G records at a time, each
@@ -765,24 +684,6 @@ __device__ __forceinline__ void size_records(const AttArgs& a, uint64_t t0, uint
   }
 }
 
-// Block-wide exclusive scan of one value per thread; *total receives the sum.
-template <int T>
-__device__ __forceinline__ uint64_t block_excl(uint64_t x, uint64_t* s_wave, uint64_t* total) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const uint64_t incl = wscan(x);
-  if (lane == 63) s_wave[w] = incl;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < T / 64; ++k) {
-    before += k < w ? s_wave[k] : 0;
-    all += s_wave[k];
-  }
-  __syncthreads();  // (s_wave is rewritten by the next scan)
-  *total = all;
-  return before + incl - x;
-}
-
 // The tile's exclusive base: thread t watches predecessor tile - 1 - t (T a round); the nearest
 // inclusive prefix (P) ends the walk, the aggregates (A) nearer than it are added.
 template <int T>
@@ -814,58 +715,41 @@ __device__ uint64_t lookback_tiles(uint64_t* status, uint64_t tile, uint32_t* s_
 }
 
 // Launch 1: every record's size, the tile's scan, its base by look-back, offsets out.
-template <int T, int P, bool LOOPS = false>
+template <int T, int P>
 __device__ __forceinline__ void size_body(const AttArgs& a) {
-  __shared__ uint64_t s_wave[T / 64], s_part[T / 64];
+  __shared__ uint64_t s_part[T / 64];
   __shared__ uint32_t s_first, s_tile;
   const int tid = threadIdx.x;
   if (tid == 0) s_tile = atomicAdd(a.ticket, 1u);
   __syncthreads();
   const uint64_t tile = s_tile, t0 = tile * (uint64_t)(T * P);
   uint64_t sz[P];
-  if (LOOPS) {  // (A/B: round 5's first form, each record's loops in turn)
-#pragma unroll
-    for (int q = 0; q < P; ++q) {
-      const uint64_t i = t0 + (uint64_t)q * T + tid;
-      sz[q] = i < a.n ? record_size(a, i) : 0;
-    }
-  } else {
-    size_records<T, P, 2>(a, t0, sz);
-  }
+  size_records<T, P, 2>(a, t0, sz);
   uint64_t ex[P], run = 0;
-  if (LOOPS) {
+  // the P rows' scans together: P independent wave scans (their shuffles interleave), one
+  // barrier, then each row's offset from the waves' totals -- where a block scan per row
+  // took two barriers each
+  __shared__ uint64_t s_rows[P][T / 64];
+  const int lane = tid & 63, w = tid >> 6;
+  uint64_t incl[P];
 #pragma unroll
-    for (int q = 0; q < P; ++q) {
-      uint64_t tot;
-      ex[q] = run + block_excl<T>(sz[q], s_wave, &tot);
-      run += tot;
+  for (int q = 0; q < P; ++q) incl[q] = wscan(sz[q]);
+  if (lane == 63) {
+#pragma unroll
+    for (int q = 0; q < P; ++q) s_rows[q][w] = incl[q];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < P; ++q) {
+    uint64_t before = 0, all = 0;
+#pragma unroll
+    for (int k = 0; k < T / 64; ++k) {
+      const uint64_t x = s_rows[q][k];
+      before += k < w ? x : 0;
+      all += x;
     }
-  } else {
-    // the P rows' scans together: P independent wave scans (their shuffles interleave), one
-    // barrier, then each row's offset from the waves' totals -- where a block scan per row
-    // took two barriers each
-    __shared__ uint64_t s_rows[P][T / 64];
-    const int lane = tid & 63, w = tid >> 6;
-    uint64_t incl[P];
-#pragma unroll
-    for (int q = 0; q < P; ++q) incl[q] = wscan(sz[q]);
-    if (lane == 63) {
-#pragma unroll
-      for (int q = 0; q < P; ++q) s_rows[q][w] = incl[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < P; ++q) {
-      uint64_t before = 0, all = 0;
-#pragma unroll
-      for (int k = 0; k < T / 64; ++k) {
-        const uint64_t x = s_rows[q][k];
-        before += k < w ? x : 0;
-        all += x;
-      }
-      ex[q] = run + before + incl[q] - sz[q];
-      run += all;
-    }
+    ex[q] = run + before + incl[q] - sz[q];
+    run += all;
   }
   if (tid == 0) st_status(a.status + tile, (tile == 0 ? kFlagP : kFlagA) | run);
   const uint64_t base = tile == 0 ? 0 : lookback_tiles<T>(a.status, tile, &s_first, s_part);
@@ -881,125 +765,39 @@ __device__ __forceinline__ void size_body(const AttArgs& a) {
 extern "C" __global__ void __launch_bounds__(kSizeThreads) pz_wire_att_size_kernel(AttArgs a) {
   size_body<kSizeThreads, kSizePer>(a);
 }
-#ifdef PZ_AB_BUILD
-extern "C" __global__ void __launch_bounds__(512) pz_wire_att_size_512x4_kernel(AttArgs a) { size_body<512, 4>(a); }
-extern "C" __global__ void __launch_bounds__(256) pz_wire_att_size_256x8_kernel(AttArgs a) { size_body<256, 8>(a); }
-extern "C" __global__ void __launch_bounds__(1024) pz_wire_att_size_1024x2_kernel(AttArgs a) { size_body<1024, 2>(a); }
-extern "C" __global__ void __launch_bounds__(kSizeThreads) pz_wire_att_size_loops_kernel(AttArgs a) {
-  size_body<kSizeThreads, kSizePer, true>(a);
-}
-#endif
-
 // Launch 2: four records per wave, one per DPP row.  63 VGPRs; left alone the SGPRs (about
 // 100) hold it at 7 waves per SIMD.  Capped at 8 (28 SGPRs spill to VGPR lanes): 0.432 ->
 // 0.383 ms per 1M-record encode (tools/wire_att_probe.py r2t, same-process A/B).
-#define PZ_ATT_WRITE(NAME, DST, NTF)                                                                 \
-  extern "C" __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(8, 8)))  \
-  NAME(AttArgs a) {                                                                                  \
-    __shared__ __attribute__((aligned(16))) uint8_t stage[kWaves][kRecs][kStageAlloc];              \
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                                  \
-    wire_att_write_rows<DST, NTF>(a, stage[w], ((uint64_t)blockIdx.x * kWaves + w) * kRecs);         \
-  }
-PZ_ATT_WRITE(pz_wire_att_write_kernel, 2, 0)
-#ifdef PZ_AB_BUILD
-PZ_ATT_WRITE(pz_wire_att_write_bytes_kernel, 0, 0)
-PZ_ATT_WRITE(pz_wire_att_write_aligned_kernel, 1, 0)
-PZ_ATT_WRITE(pz_wire_att_write_sigloop_kernel, 3, 0)  // the product with the byte-loop signature varints
-PZ_ATT_WRITE(pz_wire_att_write_nts_kernel, 2, 1)  // nontemporal 16-B output stores
-PZ_ATT_WRITE(pz_wire_att_write_ntsl_kernel, 2, 3)  // + nontemporal head loads
-// 1 round 4's three launches, 2 this scan + byte-wise stage, 3-5 other sizing tiles, 6 the
-// aligned-dword stage, 7 the sizing loops, 8 byte-loop signature varints, 9 nontemporal output
-// stores, 10 + nontemporal head loads
-int g_att_variant = 0;
-#endif
+extern "C" __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(8, 8)))
+pz_wire_att_write_kernel(AttArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t stage[kWaves][kRecs][kStageAlloc];
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  wire_att_write_rows(a, stage[w], ((uint64_t)blockIdx.x * kWaves + w) * kRecs);
+}
 
-uint64_t att_tiles(uint64_t n) { return (n + 2047) / 2048; }  // (scratch: the smallest tile of any geometry)
+// (scratch: a status word per 2,048 records -- twice what the sizing tiles need; the size
+// callers were told before the other tile geometries were removed)
+uint64_t att_tiles(uint64_t n) { return (n + 2047) / 2048; }
 
-hipError_t launch_write(const AttArgs& a, bool dst, hipStream_t s) {
+hipError_t launch_write(const AttArgs& a, hipStream_t s) {
   if (!a.n) return hipSuccess;
-  const void* k = (const void*)pz_wire_att_write_kernel;
-#ifdef PZ_AB_BUILD
-  if (!dst) k = (const void*)pz_wire_att_write_bytes_kernel;
-  if (g_att_variant == 6) k = (const void*)pz_wire_att_write_aligned_kernel;
-  if (g_att_variant == 8) k = (const void*)pz_wire_att_write_sigloop_kernel;
-  if (g_att_variant == 9) k = (const void*)pz_wire_att_write_nts_kernel;
-  if (g_att_variant == 10) k = (const void*)pz_wire_att_write_ntsl_kernel;
-#else
-  (void)dst;
-#endif
-  void* args[] = {const_cast<AttArgs*>(&a)};
-  return hipLaunchKernel(k, dim3((uint32_t)((a.n + kRecs * kWaves - 1) / (kRecs * kWaves))), dim3(kThreads), args, 0,
-                         s);
+  hipLaunchKernelGGL(pz_wire_att_write_kernel, dim3((uint32_t)((a.n + kRecs * kWaves - 1) / (kRecs * kWaves))),
+                     dim3(kThreads), 0, s, a);
+  return hipGetLastError();
 }
 
 // sizes + offsets (status words reset first), then the writes
-hipError_t launch_two(AttArgs a, void* scratch, bool dst, hipStream_t s) {
+hipError_t launch_encode(AttArgs a, void* scratch, hipStream_t s) {
   if (!a.n) return hipMemsetAsync(a.offs, 0, 8, s);
-  const void* k = (const void*)pz_wire_att_size_kernel;
-  uint32_t T = kSizeThreads, tile = kSizeTile;
-#ifdef PZ_AB_BUILD
-  if (g_att_variant == 3) k = (const void*)pz_wire_att_size_512x4_kernel, T = 512, tile = 2048;
-  if (g_att_variant == 4) k = (const void*)pz_wire_att_size_256x8_kernel, T = 256, tile = 2048;
-  if (g_att_variant == 5) k = (const void*)pz_wire_att_size_1024x2_kernel, T = 1024, tile = 2048;
-  if (g_att_variant == 7) k = (const void*)pz_wire_att_size_loops_kernel;
-#endif
-  const uint64_t tiles = (a.n + tile - 1) / tile;
+  const uint64_t tiles = (a.n + kSizeTile - 1) / kSizeTile;
   a.status = static_cast<uint64_t*>(scratch);
   a.ticket = reinterpret_cast<uint32_t*>(a.status + tiles);
   hipError_t e = hipMemsetAsync(scratch, 0, tiles * 8 + 8, s);
   if (e != hipSuccess) return e;
-  void* args[] = {&a};
-  if ((e = hipLaunchKernel(k, dim3((uint32_t)tiles), dim3(T), args, 0, s)) != hipSuccess) return e;
-  return launch_write(a, dst, s);
-}
-
-#ifdef PZ_AB_BUILD
-// ---- round 4's three launches: size kernel, rocPRIM scan, byte-wise write kernel ----------------
-extern "C" __global__ void __launch_bounds__(kThreads) pz_wire_att_size_r4_kernel(AttArgs a) {
-  const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= a.n) return;
-  Head h;
-  load_head(a, i, h);
-  uint64_t body = 0, sigb = 0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    body += h.v[k] ? 1 + vlen(h.v[k]) : 0;
-    body += h.bl[k] ? 1 + vlen(h.bl[k]) + h.bl[k] : 0;
-  }
-#pragma unroll 4
-  for (uint64_t e = h.o0; e < h.o1; ++e) {
-    const uint64_t l = a.ooff[e + 1] - a.ooff[e];
-    body += 1 + vlen(l) + l;
-  }
-#pragma unroll 4
-  for (uint64_t e = h.s0; e < h.s1; ++e) sigb += vlen(a.sig[e]);
-  body += sigb ? 1 + vlen(sigb) + sigb : 0;
-  a.sizes[i] = a.field ? a.tag_len + vlen(body) + body : body;
-}
-
-
-size_t scan_bytes(uint64_t n) {
-  size_t bytes = 0;
-  (void)rocprim::inclusive_scan(nullptr, bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)n,
-                                rocprim::plus<uint64_t>(), (hipStream_t)0);
-  return (bytes + 255) & ~size_t(255);
-}
-
-hipError_t launch_three(AttArgs a, void* scratch, hipStream_t s) {
-  a.sizes = static_cast<uint64_t*>(scratch);
-  hipError_t e = hipMemsetAsync(a.offs, 0, 8, s);
-  if (e != hipSuccess || !a.n) return e;
-  hipLaunchKernelGGL(pz_wire_att_size_r4_kernel, dim3((uint32_t)((a.n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                     a);
+  hipLaunchKernelGGL(pz_wire_att_size_kernel, dim3((uint32_t)tiles), dim3(kSizeThreads), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  size_t bytes = scan_bytes(a.n);
-  e = rocprim::inclusive_scan(static_cast<uint8_t*>(scratch) + ((a.n * 8 + 255) & ~uint64_t(255)), bytes, a.sizes,
-                              a.offs + 1, (size_t)a.n, rocprim::plus<uint64_t>(), s);
-  if (e != hipSuccess) return e;
-  return launch_write(a, false, s);
+  return launch_write(a, s);
 }
-
-#endif
 
 int att_args(const pz_attestation_cols* c, uint64_t n, uint32_t field_num, AttArgs* a) {
   if (!c) return fail(PZ_EINVAL, "columns are null");
@@ -1034,14 +832,6 @@ int att_args(const pz_attestation_cols* c, uint64_t n, uint32_t field_num, AttAr
   return PZ_OK;
 }
 
-hipError_t launch_encode(const AttArgs& a, void* scratch, hipStream_t s) {
-#ifdef PZ_AB_BUILD
-  if (g_att_variant == 1) return launch_three(a, scratch, s);
-  if (g_att_variant == 2) return launch_two(a, scratch, false, s);
-#endif
-  return launch_two(a, scratch, true, s);
-}
-
 }  // namespace
 }  // namespace pz
 
@@ -1050,12 +840,7 @@ using namespace pz;
 extern "C" {
 
 uint64_t pz_wire_attestations_scratch_bytes(uint64_t n) {
-  const uint64_t two = ((att_tiles(n) * 8 + 8 + 255) & ~uint64_t(255));
-#ifdef PZ_AB_BUILD
-  return std::max<uint64_t>(two, ((n * 8 + 255) & ~uint64_t(255)) + scan_bytes(n));
-#else
-  return std::max<uint64_t>(two, 256);
-#endif
+  return std::max<uint64_t>((att_tiles(n) * 8 + 8 + 255) & ~uint64_t(255), 256);
 }
 
 uint64_t pz_wire_attestations_bound(uint64_t n, uint64_t bytes_total, uint64_t n_oblique, uint64_t n_sig) {
@@ -1145,11 +930,3 @@ int pz_wire_attestations(const pz_attestation_cols* c, uint64_t n, uint32_t fiel
 }
 
 }  // extern "C"
-
-#ifdef PZ_AB_BUILD
-extern "C" int pz_debug_set_att_write_variant(int v) {
-  const int old = pz::g_att_variant;
-  pz::g_att_variant = v;
-  return old;
-}
-#endif

@@ -624,29 +624,12 @@ def test_gpu_replay_vote_queue_forms_vs_c_port(forms):
 
 
 @pytest.mark.gpu
-@pytest.mark.ab
-@pytest.mark.parametrize("path,epack,prep", [("segments", "copy", ""), ("packed", "copy", ""), ("direct", "direct", ""),
-                                             ("direct", "direct", "merged"), ("direct", "copy", "merged")])
-def test_ab_replay_vote_queue_paths_vs_c_port(path, epack, prep, monkeypatch):
-    """The A/B library's measured-and-dropped ways a flush reaches the device (PZ_VOTE_PATH: the
-    queue's arrays staged by one multi-segment copy, or round 3's packed arena), the
-    transitions' epoch kernels reading their inputs in place (PZ_EPOCH_PACK=direct), and the
-    stateRecalc's tally and epoch count blocks in one grid (PZ_EPOCH_PREP=merged:
-    pz_vote_words_count_kernel)."""
-    monkeypatch.setenv("PZ_VOTE_PATH", path)
-    monkeypatch.setenv("PZ_EPOCH_PACK", epack)
-    monkeypatch.setenv("PZ_EPOCH_PREP", prep)
-    _vote_queue_chain()
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("pipeline", ["0", pytest.param("1", marks=pytest.mark.ab)])
-def test_gpu_malformed_block_ends_the_call_there(pipeline, monkeypatch):
+@pytest.mark.parametrize("pipeline", ["0"])
+def test_gpu_malformed_block_ends_the_call_there(pipeline):
     """A block that is not a canonical encoding ends the call there with PZ_EINVAL, the blocks
-    before it processed (as the reference's sync service handles each block as it arrives), in
-    the batch path and in the pipelined one (PZ_CHAIN_PIPELINE=1: calls of >= 1,024 blocks parse
-    and hash a chunk ahead of the walk).  The chain is then exactly the chain of those blocks."""
-    monkeypatch.setenv("PZ_CHAIN_PIPELINE", pipeline)
+    before it processed (as the reference's sync service handles each block as it arrives).  The
+    chain is then exactly the chain of those blocks.  (The parameter is what is left of a second,
+    pipelined walk, since removed: it keeps the test's id.)"""
     from prysm_amd import _lib
     from prysm_amd.blockchain import BeaconChain, serialize_blocks
     blocks = synth.chain_blocks(1024, 1100, seed=3)

@@ -38,16 +38,6 @@ def main():
     digest = int(st.sum().item()) * 31 + int(cm.sum().item()) * 7 + int(ps.sum().item())
     print("attcheck: %d attestations  %.4f ms  %.1f G/s  result digest %d" % (natt, ms, natt / ms / 1e6, digest),
           flush=True)
-    dll = _lib.lib.dll
-    if hasattr(dll, "pz_debug_set_attcheck_variant"):  # same-process A/B (PZ_PROBE_LIB=build/ab/...)
-        # 0 the product (persistent blocks, the committee table in LDS, 3 blocks per CU), 1 round 5's
-        # x2 kernel (the walk in global memory), 2 / 3 the product at 2 / 1 blocks per CU
-        for v in [int(x) for x in os.environ.get("VARIANTS", "0,1,2,3,0,1").split(",")]:
-            dll.pz_debug_set_attcheck_variant(v)
-            ms = timed()
-            d = int(st.sum().item()) * 31 + int(cm.sum().item()) * 7 + int(ps.sum().item())
-            print("  variant %d  %.4f ms  same digest %s" % (v, ms, d == digest), flush=True)
-        dll.pz_debug_set_attcheck_variant(0)
 
 
 if __name__ == "__main__":

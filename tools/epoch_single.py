@@ -1,8 +1,7 @@
 """The single-instance epoch's latency (tools/ only): python tools/epoch_single.py
 bench.py's epoch.single_instance measure (one 65,536-validator instance, the single launch,
-HIP-event pair per step, median) per A/B form of the single launch (PZ_PROBE_LIB=build/ab/...,
-ONE=a,b,...: pz_debug_set_one_variant -- 0 the product, 1 the piece positions from the item
-table, round 5's form)."""
+HIP-event pair per step, median).  TRACE=1 with PZ_PROBE_LIB=build/ab/libprysm_hip.so prints the
+traced kernel's phase stamps (pz_debug_set_one_trace)."""
 import os
 import sys
 import types
@@ -17,8 +16,6 @@ if os.environ.get("PZ_PROBE_LIB"):  # (A/B: another build of the library)
     _lib.library_path = os.environ["PZ_PROBE_LIB"]
 import bench  # noqa: E402
 
-VARIANTS = [int(x, 0) for x in os.environ.get("ONE", "0,1,0,1").split(",") if x]
-
 
 def main():
     dev = torch.device("cuda", 0)
@@ -27,16 +24,10 @@ def main():
     dll = _lib.lib.dll
     if os.environ.get("TRACE") == "1":
         return trace(args, dev, shuffled, dll)
-    ab = hasattr(dll, "pz_debug_set_one_variant")
-    for v in VARIANTS if ab else [0]:
-        if ab:
-            dll.pz_debug_set_one_variant(v)
-        r = bench.epoch_single_instance(args, torch, dev, 65536, shuffled)
-        print("variant %d: device %.4f ms median (net of the event floor %.4f)  back-to-back %.4f ms  window pass %.4f"
-              % (v, r["device_ms_median"], r["device_ms_net_of_event_floor"], r["back_to_back_ms_per_step"],
-                 r["window_pass"]["device_ms_median"]), flush=True)
-    if ab:
-        dll.pz_debug_set_one_variant(0)
+    r = bench.epoch_single_instance(args, torch, dev, 65536, shuffled)
+    print("device %.4f ms median (net of the event floor %.4f)  back-to-back %.4f ms  window pass %.4f"
+          % (r["device_ms_median"], r["device_ms_net_of_event_floor"], r["back_to_back_ms_per_step"],
+             r["window_pass"]["device_ms_median"]), flush=True)
 
 
 def trace(args, dev, shuffled, dll):

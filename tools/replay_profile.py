@@ -35,7 +35,7 @@ def main():
              "walk(all)", "process(all)", "count_atts", "flush_arena_wait", "msg_send",
              "msg_hash_log", "msg_wait", "totals_wait", "poll_fallbacks(count)", "vote_id_rows(count)"]
     # AB=VAR: alternate the environment variable VAR over the values AB_VALUES (default "0,1")
-    # across the replays (an A/B of a per-call knob such as PZ_VOTE_PATH in one process); REPS
+    # across the replays (an A/B of a per-call environment switch in one process); REPS
     # replays per value
     ab = os.environ.get("AB")
     vals = os.environ.get("AB_VALUES", "0,1").split(",")

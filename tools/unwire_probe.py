@@ -96,21 +96,6 @@ def records(reps, n):
                       e_scr.data_ptr(), sh)
 
     d_ms, e_ms = timed([decode, encode], reps)
-    dll = _lib.lib.dll
-    if hasattr(dll, "pz_debug_set_unwire_variant"):  # same-process A/B (PZ_PROBE_LIB=build/ab/...)
-
-        def variant(v):
-            def run():
-                dll.pz_debug_set_unwire_variant(v)
-                decode()
-                dll.pz_debug_set_unwire_variant(0)
-            return run
-
-        p_ms, b_ms, l_ms = timed([decode, variant(1), variant(2)], reps)
-        print("  product %.3f ms; copies byte by byte %.3f ms; walks with a load per byte %.3f ms (medians, "
-              "alternating)"
-              % (np.median(p_ms), np.median(b_ms), np.median(l_ms)), flush=True)
-        decode()
     # algorithmic bytes from shapes: the records and their spans read once, every column written once
     col_bytes = sum(int(cols[k].nbytes) for k in wire.ATT_COLS)
     d_alg = n * 512 + 2 * n * 8 + col_bytes + n * (8 + 1 + 4)  # + n_oblique, last_byte, status

@@ -45,22 +45,6 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / reps
-    dll = _lib.lib.dll
-    if hasattr(dll, "pz_debug_set_att_write_variant"):  # same-process A/B (PZ_PROBE_LIB=build/ab/...)
-        # product / byte-loop sig varints / sizing loops (r5 first form) / aligned-dword stage;
-        # WATT_VARIANTS=a,b,... another list
-        vs = [int(x) for x in os.environ.get("WATT_VARIANTS", "0,8,7,6,0,8,7").split(",")]
-        for v in vs:
-            dll.pz_debug_set_att_write_variant(v)
-            e0.record()
-            for _ in range(reps):
-                run()
-            e1.record()
-            torch.cuda.synchronize()
-            ok_v = bool(np.array_equal(out[:n * 512].cpu().numpy(), synth.attestation_records_512(n, seed=2).reshape(-1)))
-            print("  variant %d  encode %.3f ms  parity=%s" % (v, e0.elapsed_time(e1) / reps, ok_v), flush=True)
-        dll.pz_debug_set_att_write_variant(0)
-        run()
     # the CSR hash kernel over the encoded records (the encode + hash leg's second launch)
     dig = torch.empty(n * 32, dtype=torch.uint8, device="cuda")
 

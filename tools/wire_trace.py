@@ -39,7 +39,7 @@ def main():
         run()
     ref = out[:int(tot.item())].clone()
     dll.pz_debug_set_wire_trace(ctypes.c_void_p(trace.data_ptr()))
-    variant = int(sys.argv[1]) if len(sys.argv) > 1 else 32  # 34: no stage build, 36: no look-back, 288: time the first poll
+    variant = 32  # the product kernel plus the stamps
     dll.pz_debug_set_wire_variant(variant)
     res = []
     for rep in range(5):
@@ -47,7 +47,7 @@ def main():
         torch.cuda.synchronize()
         t = trace.cpu().numpy().reshape(nt, 16)
         ts = t[:, :6].astype(np.int64)
-        same = bool(torch.equal(out[:ref.numel()], ref)) if variant in (32, 544) else None
+        same = bool(torch.equal(out[:ref.numel()], ref))
         t0 = ts[:, 0].min()
         d = np.diff(ts, axis=1) * 10 / 1e3  # us (100 MHz)
         life = (ts[:, 5] - ts[:, 0]) * 10 / 1e3
@@ -74,16 +74,13 @@ def main():
                                         "p90": float(np.percentile(t[1:, 10], 90))},
             "build_end_last_wave_after_thread0_us": round(float(np.median((t[:, 11] - ts[:, 3]) * 10 / 1e3)), 2),
             "repolls_most_of_any_thread": {"median": float(np.median(t[1:, 12])), "p90": float(np.percentile(t[1:, 12], 90))},
-            "first_window_round_trip_us": (round(float(np.median((t[1:, 8] - ts[1:, 2]) * 10 / 1e3)), 2)
-                                           if variant & 256 else None),
             # thread 0 inside the look-back (tiles > 0): build end -> every flag seen -> window
             # reduced (its barrier) -> the phase's end
             "lookback_flags_us": round(float(np.median((t[1:, 13] - ts[1:, 3]) * 10 / 1e3)), 2),
             "lookback_reduce_us": round(float(np.median((t[1:, 14] - t[1:, 13]) * 10 / 1e3)), 2),
             "lookback_tail_us": round(float(np.median((ts[1:, 4] - t[1:, 14]) * 10 / 1e3)), 2),
             "lookback_return_us": round(float(np.median((t[1:, 15] - t[1:, 14]) * 10 / 1e3)), 2),
-            "prefix_store_us": (round(float(np.median((t[1:, 8] - t[1:, 15]) * 10 / 1e3)), 2)
-                                if not variant & 256 else None),
+            "prefix_store_us": round(float(np.median((t[1:, 8] - t[1:, 15]) * 10 / 1e3)), 2),
         })
     dll.pz_debug_set_wire_variant(0)
     dll.pz_debug_set_wire_trace(None)
