@@ -835,6 +835,75 @@ int pz_vote_cache_read(pz_vote_cache* cache, uint8_t* hashes, uint64_t* totals, 
  * zeros when absent) and *present = the map has the entry.  Same waiting and errors as read. */
 int pz_vote_cache_voters(pz_vote_cache* cache, const uint8_t hash[32], uint32_t* words, int* present);
 
+/* ---- R: ActiveState.PendingAttestations resident on the device --------------------------------
+ * The attestations a block contributes (processedAttestations, blockchain/service.go:280-301)
+ * become ActiveState.PendingAttestations (computeNewActiveState, core.go:223-237) and feed the
+ * cycle transition: processCrosslinks, CalculateRewards and the Slot > lastStateRecalc filter
+ * (core.go:433-457).  The handle owns that list on one device as the full pz_attestation_cols
+ * column set (three scalars, three bytes CSRs, the element CSR of field 7 with oblique_first,
+ * aggregate_sig with aggregate_sig_first) plus two columns: `committee` (u32, the checks'
+ * committee id) and `shard32` (u32, shard_id saturated to UINT32_MAX: a shard of 2^32 or more
+ * still raises the epoch's PZ_XLERR_SHARD).  It is appended to from the decoder's columns and the
+ * checks' outputs, pruned by slot, and read in place: as the epoch kernels' attestation inputs
+ * (pz_epoch_batch.bits / boffs = attester_bitfield(+_offs), att_comm = committee, att_shard =
+ * shard32), as pz_attestation_cols for pz_dev_wire_attestations(field_num = 1) (the stored
+ * ActiveState's field 1, types/state.go:141), and as the crosslink winners' ShardBlockHash.
+ *
+ * caps[7], fixed at creation, in the order of the decoder's totals with "rows" first: rows,
+ * justified_block_hash bytes, shard_block_hash bytes, bitfield bytes, elements, element bytes,
+ * sig values.  Seven running counts live on the device.  Two buffer sets ping-pong for the prune;
+ * every bytes column has the 4 readable bytes of slack the digest kernels' contract asks for.
+ *
+ * Append and prune are the same four dependent launches on the caller's stream (size, scan,
+ * commit, write: DESIGN.md §3); no workgroup waits for another.  A call that would exceed any of
+ * the seven capacities changes nothing and sets the sticky capacity error: it lands whole or not
+ * at all.  Calls on one pool are ordered by the caller (one stream, or its own events).
+ * Thread-safe per handle. */
+typedef struct pz_att_pool pz_att_pool;
+/* types.NewActiveState's pending list (types/state.go:39), empty.  PZ_EINVAL: a zero row capacity. */
+int      pz_att_pool_new(const uint64_t caps[7], int device, pz_att_pool** out);
+void     pz_att_pool_free(pz_att_pool* pool);
+/* The scratch an append of n rows needs (no reference counterpart). */
+uint64_t pz_att_pool_scratch_bytes(uint64_t n);
+/* processedAttestations = append(processedAttestations, attestation) (service.go:300) followed by
+ * NewPendingAttestation / append(PendingAttestations, ...) (core.go:223-237): appends, in row
+ * order, every row of `a` with status[i] == PZ_ATT_PROCESSED and, when take is given, take[i] != 0.
+ * pz_attestation_cols' NULL rules hold (a NULL scalar is 0, NULL offsets are empty ranges).
+ * Offsets must be non-decreasing, as the decoder's are; a kept row with an inverted range lands
+ * with zero scalars, six empty ranges and committee UINT32_MAX, and sets a sticky PZ_EINVAL bit.
+ * PZ_EINVAL, before any launch: with n > 0 a NULL a, status or committee, offsets without their
+ * data column (oblique_first also wants oblique_offs), d_scratch NULL or not 16-byte aligned.
+ * n == 0 launches nothing.  Device pointers, caller's stream, asynchronous. */
+int pz_dev_att_pool_append(pz_att_pool* pool, const pz_attestation_cols* a, uint64_t n, const int32_t* status,
+                           const uint32_t* committee, const uint8_t* take /* optional */, void* d_scratch, void* stream);
+/* The same append (service.go:300, core.go:223-237) over host pointers (ranges start at 0),
+ * synchronous.  Errors the kernels find are sticky and reported by pz_att_pool_counts /
+ * pz_att_pool_read, not here. */
+int pz_att_pool_append(pz_att_pool* pool, const pz_attestation_cols* a, uint64_t n, const int32_t* status,
+                       const uint32_t* committee, const uint8_t* take /* optional */);
+/* stateRecalc's filter, core.go:444-450: keeps, in order, the rows with slot > last_state_recalc.
+ * Writes into the other buffer set, then the sets swap.  Caller's stream, asynchronous. */
+int pz_dev_att_pool_prune(pz_att_pool* pool, uint64_t last_state_recalc, void* stream);
+/* len(PendingAttestations()) (types/state.go:164) and the six other counts, in caps' order.  Waits for the last call's
+ * stream.  The sticky error comes first (PZ_EINVAL for an inverted range, else PZ_ERANGE when a
+ * call was dropped for capacity); the counts are filled all the same. */
+int pz_att_pool_counts(pz_att_pool* pool, uint64_t counts[7]);
+/* PendingAttestations() (types/state.go:164) as device pointers into the live buffer set,
+ * valid until the next prune or free; any of the three outputs may be NULL.  No device call. */
+int pz_att_pool_view(pz_att_pool* pool, pz_attestation_cols* cols, const uint32_t** committee, const uint32_t** shard32);
+/* Host download of PendingAttestations() (types/state.go:164; tests, persistence): the fourteen columns of out (its
+ * n_oblique, last_byte and status are not touched; a NULL column is skipped) and committee
+ * (optional).  caps: as pz_unwire_attestations' (the rows are sized from pz_att_pool_counts);
+ * PZ_ERANGE, nothing written, when a count exceeds its capacity.  Same waiting and sticky error as
+ * pz_att_pool_counts, the outputs filled all the same. */
+int pz_att_pool_read(pz_att_pool* pool, const pz_attestation_cols_out* out, uint32_t* committee, const uint64_t caps[6]);
+/* Host, synchronous: field 5 (ShardBlockHash) of the named rows, out[offs[k] .. offs[k+1]) for
+ * rows[k]; offs holds nrows + 1 entries: what a crosslink winner writes into its record,
+ * core.go:550-554.  PZ_EINDEX for a row the pool does not hold, PZ_ERANGE (offs filled) when the
+ * bytes exceed cap. */
+int pz_att_pool_shard_block_hashes(pz_att_pool* pool, const uint32_t* rows, uint64_t nrows, uint8_t* out, uint64_t cap,
+                                   uint64_t* offs);
+
 typedef struct pz_block_result {
   uint8_t hash[32];      /* Block.Hash() */
   int32_t status;        /* PZ_BLOCK_* */

@@ -115,6 +115,16 @@ SIGNATURES = {
     "pz_vote_cache_tally": [vp, vp],
     "pz_vote_cache_read": [vp, vp, vp, u64, c_u64p],
     "pz_vote_cache_voters": [vp, vp, vp, c_intp],
+    "pz_att_pool_new": [vp, ctypes.c_int, vp],
+    "pz_att_pool_free": [vp],
+    "pz_att_pool_scratch_bytes": [u64],
+    "pz_dev_att_pool_append": [vp, vp, u64, vp, vp, vp, vp, vp],
+    "pz_att_pool_append": [vp, vp, u64, vp, vp, vp],
+    "pz_dev_att_pool_prune": [vp, u64, vp],
+    "pz_att_pool_counts": [vp, vp],
+    "pz_att_pool_view": [vp, vp, vp, vp],
+    "pz_att_pool_read": [vp, vp, vp, vp],
+    "pz_att_pool_shard_block_hashes": [vp, vp, u64, vp, u64, vp],
     "pz_shutdown": [],
     "pz_state_new": [u64, ctypes.c_int, vp],
     "pz_state_upload": [vp, vp, vp, vp],
@@ -268,7 +278,8 @@ _RESTYPES = {"pz_last_error": ctypes.c_char_p, "pz_chain_free": None, "pz_set_se
              "pz_wire_validators_bound": u64, "pz_wire_scratch_bytes": u64,
              "pz_wire_attestations_bound": u64, "pz_wire_attestations_scratch_bytes": u64,
              "pz_unwire_attestations_scratch_bytes": u64, "pz_unwire_blocks_scratch_bytes": u64,
-             "pz_vote_cache_free": None, "pz_vote_cache_scratch_bytes": u64}
+             "pz_vote_cache_free": None, "pz_vote_cache_scratch_bytes": u64,
+             "pz_att_pool_free": None, "pz_att_pool_scratch_bytes": u64}
 SERIAL_DEFAULT = 65536        # the library's default serial threshold (bytes)
 SERIAL_ON_GPU = (1 << 64) - 1  # pz_set_serial_threshold value that keeps every message on the GPU
 

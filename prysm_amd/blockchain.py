@@ -272,8 +272,64 @@ def digest_serialized_blocks(data, offsets, last_justified_slot, last_state_reca
 BLOCK_REJECTED, BLOCK_TALLIED, BLOCK_MIXED = 0, 1, 2  # tally_serialized_blocks' per-block report
 
 
+def _open_blocks(d, candidate=None):
+    """service.go:304-306 on the device, from :func:`_split_decode_check`'s tensors: a block is open
+    iff its folded status is PZ_OK, it has an attestation and its last attestation is PROCESSED --
+    and, when ``candidate`` (a per-block 0/1 sequence) is given, ``candidate[i]`` too.  Returns
+    ``(open, att_block, count, nproc)``: the block of every attestation row, and per block its rows
+    and how many of them are PROCESSED.  Needs ``natt > 0``."""
+    import torch
+
+    dev, n, natt, blk = d["dev"], d["n"], d["natt"], d["blk"]
+    first = blk["att_first"]
+    count = first[1:] - first[:-1]
+    att_block = blk["att_block"][:natt].long()
+    proc = (d["status"] == ATT_PROCESSED).long()
+    nproc = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, att_block, proc)
+    last_ok = proc[(first[1:] - 1).clamp(min=0)] == 1
+    open_ = (d["block_status"] == _lib.PZ_OK) & (count > 0) & last_ok
+    if candidate is not None:
+        open_ = open_ & _to_device(np.ascontiguousarray(candidate, dtype=np.uint8), dev).bool()
+    return open_, att_block, count, nproc
+
+
+def _pend(pool, d, candidate):
+    """Appends the PROCESSED rows of the open blocks of ``d`` to ``pool``; returns ``open``."""
+    import torch
+
+    if not d["natt"]:
+        return torch.zeros(d["n"], dtype=torch.bool, device=d["dev"])
+    open_, att_block, _, _ = _open_blocks(d, candidate)
+    pool.append_columns(d["att"], d["natt"], d["status"].contiguous(), d["committee"], take=open_[att_block].to(torch.uint8))
+    return open_
+
+
+def pend_serialized_blocks(pool, data, offsets, last_justified_slot, last_state_recalc, n_recent, shard_and_committees,
+                           candidate=None, device=0):
+    """processedAttestations (blockchain/service.go:280-301) of a batch of received blocks held as
+    bytes, against one chain state, into ``pool`` (a ``prysm_amd.pending.DevicePendingAttestations``):
+    the same upload, split, decode and checks as :func:`check_serialized_blocks`, then
+    ``pz_dev_att_pool_append`` over the decoded columns and the checks' outputs -- what
+    computeNewActiveState (core.go:223-237) appends to PendingAttestations.  Which rows it takes is
+    formed on the device; no column visits the host in between.
+
+    A block is open iff its bytes are accepted (folded status PZ_OK), it has at least one
+    attestation and its LAST attestation is PROCESSED (service.go:304-306); with ``candidate`` (one
+    0/1 per block) it must also have ``candidate[i]``: the walk's decision that this block reaches
+    computeNewActiveState (its parent is saved and no candidate was already chosen,
+    service.go:261-269, :331-333), which is sequential and stays the caller's.  The PROCESSED rows
+    of open blocks are appended, those of mixed blocks included: processedAttestations holds only
+    the attestations that passed.  Returns ``(block_open, att_first, att_status)``."""
+    data = np.ascontiguousarray(_lib.as_u8(data), dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    d = _split_decode_check(data if data.size else np.zeros(1, np.uint8), offsets, last_justified_slot,
+                            last_state_recalc, n_recent, shard_and_committees, device, want_committee=True)
+    open_ = _pend(pool, d, candidate)
+    return (open_.cpu().numpy(), d["blk"]["att_first"].cpu().numpy().view(np.uint64), d["status"].cpu().numpy())
+
+
 def tally_serialized_blocks(cache, data, offsets, last_justified_slot, last_state_recalc, n_recent,
-                            shard_and_committees, recent_hashes, balance, device=0):
+                            shard_and_committees, recent_hashes, balance, device=0, pending=None, candidate=None):
     """The T side of blockProcessing (blockchain/service.go:313-318: calculateBlockVoteCache over
     a block's attestations, core.go:300-345) for a batch of received blocks held as bytes, against
     one chain state, into ``cache`` (a ``prysm_amd.votes.DeviceVoteCache``): the same upload, split,
@@ -289,7 +345,11 @@ def tally_serialized_blocks(cache, data, offsets, last_justified_slot, last_stat
     att_status)``: block[i] is BLOCK_TALLIED (1), BLOCK_REJECTED (0: bad bytes, no attestation or
     the last one failed, as service.go:304-306) or BLOCK_MIXED (2); block i's attestations are
     rows att_first[i] .. att_first[i+1] of att_status.  ``recent_hashes`` as in
-    :func:`digest_serialized_blocks`; ``balance``: the validators' balances (nval)."""
+    :func:`digest_serialized_blocks`; ``balance``: the validators' balances (nval).
+
+    With ``pending`` (a ``prysm_amd.pending.DevicePendingAttestations``) the same decode also feeds
+    the pool, as :func:`pend_serialized_blocks` does (``candidate`` as there; it bears on the pool
+    alone): one upload then serves both.  With ``pending=None`` nothing about this function changes."""
     import torch
 
     data = np.ascontiguousarray(_lib.as_u8(data), dtype=np.uint8)
@@ -301,14 +361,9 @@ def tally_serialized_blocks(cache, data, offsets, last_justified_slot, last_stat
                             last_state_recalc, n_recent, shard_and_committees, device, want_committee=True)
     dev, n, natt, blk, status = d["dev"], d["n"], d["natt"], d["blk"], d["status"]
     first = blk["att_first"]
-    count = first[1:] - first[:-1]
     report = torch.zeros(n, dtype=torch.int64, device=dev)
     if natt:
-        att_block = blk["att_block"][:natt].long()
-        proc = (status == ATT_PROCESSED).long()
-        nproc = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, att_block, proc)
-        last_ok = proc[(first[1:] - 1).clamp(min=0)] == 1
-        open_ = (d["block_status"] == _lib.PZ_OK) & (count > 0) & last_ok
+        open_, att_block, count, nproc = _open_blocks(d)
         report = open_.long() * (BLOCK_TALLIED + (BLOCK_MIXED - BLOCK_TALLIED) * (nproc != count).long())
         take = (report == BLOCK_TALLIED)[att_block].to(torch.uint8)
         members = np.ascontiguousarray([v for arr in shard_and_committees for e in arr for v in e[1]] or [0],
@@ -317,11 +372,98 @@ def tally_serialized_blocks(cache, data, offsets, last_justified_slot, last_stat
         cache.tally_columns(d["att"], natt, status.contiguous(), d["committee"], d["parents_start"],
                             _to_device(recent, dev), _to_device(members, dev), _to_device(coffs, dev),
                             _to_device(np.ascontiguousarray(balance, dtype=np.uint64), dev), take=take)
+        if pending is not None:
+            _pend(pending, d, candidate)
     return (report.cpu().numpy(), first.cpu().numpy().view(np.uint64), status.cpu().numpy())
 
 
 class ChainPanic(RuntimeError):
     """The reference would panic here (index out of range / nil map / nil state)."""
+
+
+def state_recalc_device(pool, cache, state, recent_hashes, block_slot):
+    """stateRecalc (blockchain/core.go:398-497) composed from what lives on the device: ``pool`` (a
+    ``prysm_amd.pending.DevicePendingAttestations``: ActiveState.PendingAttestations), ``cache`` (a
+    ``prysm_amd.votes.DeviceVoteCache`` or anything with ``items()``; None: no entry), ``state`` (a
+    ``prysm_amd.pending.RecalcState``, advanced in place), ``recent_hashes`` = RecentBlockHashes()
+    and ``block_slot`` = the transition block's SlotNumber.
+
+    1. the 64-iteration justification loop (core.go:411-431) on the host, over ``cache.items()``
+       and ``recent_hashes[:64]``;
+    2. ``pz_dev_epoch_count`` then ``pz_dev_epoch_finish`` with one instance over the pool's view,
+       on the current stream: processCrosslinks' tallies on the pre-reward balances, the winners,
+       CalculateRewards in place and the next-cycle total (core.go:433-464);
+    3. ``scal`` and ``winner`` come back; where the reference panics ``ChainPanic`` is raised and, by
+       the kernels' contract, the balances are untouched;
+    4. the records of the shards with a winner get {dynasty, block_slot, the winner's ShardBlockHash}
+       (core.go:549-555);
+    5. the pool is pruned to ``slot > last_state_recalc`` (core.go:444-450);
+    6. the new scalars (core.go:467-478): last_state_recalc + 64, justified / streak / finalized,
+       total_deposits = the next-cycle balance -- and current_dynasty 0, which the reference's new
+       state leaves unset.
+    Returns the winners (one attestation row per record, 0xFFFFFFFF: none)."""
+    import torch
+
+    from prysm_amd import pb
+
+    M64 = (1 << 64) - 1
+    lsr = state.last_state_recalc
+    recent = _recent_array(recent_hashes)
+    if len(recent) < 64:
+        raise ChainPanic("stateRecalc: RecentBlockHashes()[i], index out of range (core.go:413)")
+    totals = cache.items() if cache is not None else {}
+    streak, justified, finalized = state.justified_streak, state.last_justified_slot, state.last_finalized_slot
+    for i in range(64):
+        slot = (lsr - 64 + i) & M64
+        bal = totals.get(recent[i].tobytes(), 0)
+        if (3 * bal) & M64 >= (2 * state.total_deposits) & M64:
+            justified = max(justified, slot)
+            streak = (streak + 1) & M64
+        else:
+            streak = 0
+        if streak >= 65 and ((slot - 64) & M64) > finalized:
+            finalized = (slot - 64) & M64
+
+    dev = state.balance.device
+    n, nrec = state.nval, len(state.crosslink_records)
+    b = pool.epoch_batch()
+    natt = int(b.natt)
+    i64 = lambda v: _to_device(np.array(v, dtype=np.uint64), dev)  # noqa: E731
+    dynasty, tdep = i64([state.current_dynasty]), i64([state.total_deposits])
+    rec_dynasty = i64([r.dynasty for r in state.crosslink_records] or [0])
+    winner = torch.full((max(nrec, 1),), -1, dtype=torch.int32, device=dev)
+    red = torch.zeros(_lib.SCAL_COUNT + 2 * max(natt, 1), dtype=torch.int64, device=dev)
+    act_mask = torch.zeros((n + 63) // 64, dtype=torch.int64, device=dev)
+    blk_cnt = torch.zeros((n + 2047) // 2048 + 1, dtype=torch.int32, device=dev)
+    act_list = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    b.nval, b.val_offset, b.nval_global, b.kind = n, 0, n, _lib.KIND_ACTIVE
+    b.balance, b.start, b.end = state.balance.data_ptr(), state.start.data_ptr(), state.end.data_ptr()
+    b.dynasty, b.total_deposit = dynasty.data_ptr(), tdep.data_ptr()
+    b.pop_rank, b.pop_world = 0, 1
+    b.committee, b.coffs = state.members.data_ptr(), state.coffs.data_ptr()
+    b.nrec, b.rec_dynasty, b.winner = nrec, rec_dynasty.data_ptr(), winner.data_ptr()
+    b.scal = red.data_ptr()
+    b.vote, b.total = red[_lib.SCAL_COUNT:].data_ptr(), red[_lib.SCAL_COUNT + max(natt, 1):].data_ptr()
+    b.act_mask, b.blk_cnt, b.act_list = act_mask.data_ptr(), blk_cnt.data_ptr(), act_list.data_ptr()
+    sh = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    lib.call("pz_dev_epoch_count", ctypes.byref(b), sh)
+    lib.call("pz_dev_epoch_finish", ctypes.byref(b), sh)
+    scal = red[:_lib.SCAL_COUNT].cpu().numpy().view(np.uint64)
+    win = winner.cpu().numpy().view(np.uint32)[:nrec]
+    if scal[_lib.SCAL_ERR_XL]:
+        raise ChainPanic("processCrosslinks: index out of range (committee member, bitfield or shard)")
+    thr = (int(scal[_lib.SCAL_POP]) * 32 * 3) & M64 >= (state.total_deposits * 2) & M64
+    if thr and scal[_lib.SCAL_NACT] > 0 and scal[_lib.SCAL_ERR_RWD]:
+        raise ChainPanic("CalculateRewards: CheckBit index out of range (incentives.go:23)")
+    shards = np.nonzero(win != 0xFFFFFFFF)[0]
+    for s, h in zip(shards, pool.shard_block_hashes(win[shards])):
+        state.crosslink_records[int(s)] = pb.CrosslinkRecord(state.current_dynasty, h, int(block_slot))
+    pool.prune(lsr)
+    state.last_state_recalc = (lsr + 64) & M64
+    state.justified_streak, state.last_justified_slot, state.last_finalized_slot = streak, justified, finalized
+    state.total_deposits = int(scal[_lib.SCAL_NEXT_BAL])
+    state.current_dynasty = 0
+    return win
 
 
 def serialize_blocks(blocks):

@@ -1,0 +1,631 @@
+// ActiveState.PendingAttestations resident on one device, for gfx950.
+//
+// The attestations a block contributes (processedAttestations, blockchain/service.go:280-301)
+// become pending attestations (NewPendingAttestation, computeNewActiveState, core.go:223-237) and
+// stay until stateRecalc drops those of slots up to lastStateRecalc (core.go:444-450).  The handle
+// owns them as the full pz_attestation_cols column set plus `committee` (the checks' committee id)
+// and `shard32` (shard_id saturated to u32): what the epoch kernels read as bits / boffs / att_comm
+// / att_shard, what pz_dev_wire_attestations(field_num = 1) encodes into the stored ActiveState,
+// and what a crosslink winner's ShardBlockHash is read from -- all in place.
+//
+// Append and prune are one operation: an order-preserving selection of rows of a column set into
+// another column set at a base.  Each is four dependent launches on the caller's stream, in the
+// decoder's reduce-then-scan shape (tile_scan.h); no workgroup waits for another, nothing spins,
+// nothing looks back: every cross-workgroup fact travels through a launch boundary.
+//   1 size    a lane per row, 256 rows per tile: the keep predicate and the row's seven sizes
+//             (attpool_dev.h), the tile's seven sums.
+//   2 scan    pz_unwire_scan_kernel with ncols = 7: the tiles' bases and the call's totals.
+//   3 commit  one lane: snapshots the pool's seven counts as the call's base, decides
+//             base + total <= cap for all seven, and either advances the counts or marks the call
+//             void and sets the sticky capacity bit.  A call lands whole or not at all.
+//   4 write   scans the tile's sizes again, adds the tile's base and the call's base: the five
+//             offsets columns are written once; scalars, committee, shard32, the bytes ranges, the
+//             element offsets (rebased) and the sig values are copied.  A range up to kApLongBytes
+//             goes lane by lane (copy_span); a longer one is copied by its whole wave.  A void call
+//             writes nothing.
+// A prune selects from the live buffer set into the other one at base 0, then the sets swap.
+//
+// Reads: only the rows' ranges of the source columns.  Writes: only inside the ranges the scan
+// assigns, which the commit has checked against the capacities.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "attpool_dev.h"
+#include "runtime.h"
+#include "tile_scan.h"
+
+namespace pz {
+namespace {
+
+constexpr int kSetBufs = 16;  // pz_attestation_cols' fourteen columns, committee, shard32
+
+}  // namespace
+}  // namespace pz
+
+struct pz_att_pool {
+  int device = 0;
+  uint64_t cap[pz::kApCols] = {};
+  std::mutex mu;
+  hipStream_t last = nullptr;  // the stream of the last call: counts / read wait for it
+  uint64_t rows_ub = 0;        // an upper bound of the rows held (a prune's grid; exact after counts)
+  int live = 0;                // which buffer set holds the rows
+  pz::DevBuf set[2][pz::kSetBufs];
+  pz::DevBuf words;    // counts[7], then the sticky error word
+  pz::DevBuf scratch;  // a prune's scratch (sized for cap[0] rows)
+  ~pz_att_pool() {
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(last);
+    for (auto& s : set)
+      for (pz::DevBuf& b : s) b.release();
+    words.release();
+    scratch.release();
+  }
+};
+
+namespace pz {
+namespace {
+
+// What one call leaves for its write launch (commit writes it).
+struct ApCall {
+  uint64_t base[kApCols];
+  uint64_t n;        // source rows
+  uint64_t is_void;  // the call did not fit: nothing is written
+};
+
+struct ApDst {
+  pz_attestation_cols_out c;  // (n_oblique, last_byte and status unused)
+  uint32_t* committee;
+  uint32_t* shard32;
+};
+
+struct ApArgs {
+  pz_attestation_cols src;
+  const uint32_t* src_committee;
+  const uint32_t* src_shard32;  // prune; an append derives it from shard_id
+  const int32_t* status;        // append's predicate
+  const uint8_t* take;
+  uint64_t last_state_recalc;  // prune's predicate
+  uint32_t prune;
+  uint64_t n;  // append: the batch's rows; prune: the host's upper bound (the count is on the device)
+  uint64_t ntiles;
+  ApDst dst;
+  uint64_t cap[kApCols];
+  uint64_t* counts;  // [7], the error word at [7]
+  uint64_t* tiles;   // [7][ntiles]
+  uint64_t* totals;  // [7]
+  ApCall* call;
+  uint64_t long_bytes;
+};
+
+uint64_t g_long_bytes = kApLongBytes;  // (the A/B library's probe varies it)
+
+__device__ __forceinline__ bool ap_keep(const ApArgs& a, uint64_t i) {
+  if (a.prune) return ap_keep_prune(a.src.slot[i], a.last_state_recalc);
+  return ap_keep_append(a.status, a.take, i);
+}
+
+// ---- 1: size -----------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(kTile) pz_att_pool_size_kernel(ApArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+  const uint64_t n = a.prune ? a.counts[kApRows] : a.n;
+  uint64_t sz[kApCols] = {0, 0, 0, 0, 0, 0, 0};
+  if (i < n && ap_keep(a, i)) {
+    const ApRow r = ap_row(a.src, i);
+    if (r.inverted) atomicOr((unsigned long long*)(a.counts + kApCols), (unsigned long long)kApErrInverted);
+#pragma unroll
+    for (int c = 0; c < kApCols; ++c) sz[c] = r.sz[c];
+  }
+  tile_sums<kApCols>(sz, a.tiles, a.ntiles);
+}
+
+// ---- 3: commit (one lane) --------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(64) pz_att_pool_commit_kernel(ApArgs a) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  uint64_t base[kApCols], total[kApCols];
+  const uint64_t rows = a.counts[kApRows];
+#pragma unroll
+  for (int c = 0; c < kApCols; ++c) {
+    base[c] = a.prune ? 0 : a.counts[c];
+    total[c] = a.totals[c];
+  }
+  const bool fits = ap_fits(base, total, a.cap);
+#pragma unroll
+  for (int c = 0; c < kApCols; ++c) {
+    a.call->base[c] = base[c];
+    if (fits) a.counts[c] = base[c] + total[c];
+  }
+  a.call->n = a.prune ? rows : a.n;
+  a.call->is_void = !fits;
+  if (!fits) atomicOr((unsigned long long*)(a.counts + kApCols), (unsigned long long)kApErrCapacity);
+}
+
+// ---- 4: write --------------------------------------------------------------------------------
+// The wave copies the long ranges of its lanes one after another: lane q's (dst, src, len) goes
+// wave-wide, every lane moves 16 unaligned bytes a step, and the tail is the last 16 bytes again
+// (len > long_bytes >= 16: every access lies inside the range).  Every lane of the wave calls.
+__device__ __forceinline__ void wave_copy_long(bool mine, uint8_t* dst, const uint8_t* src, uint64_t len) {
+  const uint32_t lane = threadIdx.x & 63;
+  uint64_t m = __ballot(mine);
+  while (m) {  // (wave-uniform)
+    const int q = __builtin_ctzll(m);
+    m &= m - 1;
+    gbyte* o = reinterpret_cast<gbyte*>((uintptr_t)__shfl((uint64_t)(uintptr_t)dst, q, 64));
+    const gbyte* s = reinterpret_cast<const gbyte*>((uintptr_t)__shfl((uint64_t)(uintptr_t)src, q, 64));
+    const uint64_t len_q = __shfl(len, q, 64);
+    constexpr uint64_t kStep = 64 * 16;  // the wave's bytes a step
+    uint64_t k = (uint64_t)lane * 16;
+    for (; k + 3 * kStep + 16 <= len_q; k += 4 * kStep) {  // four loads in flight before the stores
+      uint4 v0, v1, v2, v3;  // (named: an array here is promoted to LDS)
+      __builtin_memcpy(&v0, s + k, 16);
+      __builtin_memcpy(&v1, s + k + kStep, 16);
+      __builtin_memcpy(&v2, s + k + 2 * kStep, 16);
+      __builtin_memcpy(&v3, s + k + 3 * kStep, 16);
+      __builtin_memcpy(o + k, &v0, 16);
+      __builtin_memcpy(o + k + kStep, &v1, 16);
+      __builtin_memcpy(o + k + 2 * kStep, &v2, 16);
+      __builtin_memcpy(o + k + 3 * kStep, &v3, 16);
+    }
+    for (; k + 16 <= len_q; k += kStep) copy16(o + k, s + k);
+    if (lane == 0 && (len_q & 15)) copy16(o + len_q - 16, s + len_q - 16);
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(kTile) pz_att_pool_write_kernel(ApArgs a) {
+  if (a.call->is_void) return;  // (grid-uniform)
+  const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+  const bool keep = i < a.call->n && ap_keep(a, i);
+  ApRow r;
+#pragma unroll
+  for (int c = 0; c < kApCols; ++c) r.sz[c] = 0, r.lo[c] = 0;
+  r.inverted = false;
+  if (keep) r = ap_row(a.src, i);
+  uint64_t at[kApCols];
+  tile_excl<kApCols>(r.sz, at);
+#pragma unroll
+  for (int c = 0; c < kApCols; ++c) at[c] += a.tiles[c * a.ntiles + blockIdx.x] + a.call->base[c];
+
+  const ApDst& d = a.dst;
+  if (i == 0) {  // the ends of the offsets columns: the pool's new counts
+    uint64_t end[kApCols];
+#pragma unroll
+    for (int c = 0; c < kApCols; ++c) end[c] = a.call->base[c] + a.totals[c];
+    d.c.justified_block_hash_offs[end[kApRows]] = end[kApJbh];
+    d.c.shard_block_hash_offs[end[kApRows]] = end[kApSbh];
+    d.c.attester_bitfield_offs[end[kApRows]] = end[kApBits];
+    d.c.oblique_first[end[kApRows]] = end[kApElems];
+    d.c.oblique_offs[end[kApElems]] = end[kApElemBytes];
+    d.c.aggregate_sig_first[end[kApRows]] = end[kApSigs];
+  }
+
+  // the row's five ranges as (dst, src, bytes)
+  uint8_t* dp[5] = {d.c.justified_block_hash + at[kApJbh], d.c.shard_block_hash + at[kApSbh],
+                    d.c.attester_bitfield + at[kApBits], d.c.oblique_parent_hashes + at[kApElemBytes],
+                    reinterpret_cast<uint8_t*>(d.c.aggregate_sig + at[kApSigs])};
+  const uint8_t* sp[5] = {a.src.justified_block_hash + r.lo[kApJbh], a.src.shard_block_hash + r.lo[kApSbh],
+                          a.src.attester_bitfield + r.lo[kApBits], a.src.oblique_parent_hashes + r.lo[kApElemBytes],
+                          reinterpret_cast<const uint8_t*>(a.src.aggregate_sig + r.lo[kApSigs])};
+  const uint64_t len[5] = {r.sz[kApJbh], r.sz[kApSbh], r.sz[kApBits], r.sz[kApElemBytes], r.sz[kApSigs] * 8};
+
+  if (keep) {
+    const uint64_t row = at[kApRows];
+    const bool z = r.inverted;
+    const uint64_t shard = (!z && a.src.shard_id) ? a.src.shard_id[i] : 0;
+    d.c.slot[row] = (!z && a.src.slot) ? a.src.slot[i] : 0;
+    d.c.shard_id[row] = shard;
+    d.c.justified_slot[row] = (!z && a.src.justified_slot) ? a.src.justified_slot[i] : 0;
+    d.committee[row] = z ? 0xFFFFFFFFu : a.src_committee[i];
+    d.shard32[row] = (a.src_shard32 && !z) ? a.src_shard32[i] : ap_shard32(shard);
+    d.c.justified_block_hash_offs[row] = at[kApJbh];
+    d.c.shard_block_hash_offs[row] = at[kApSbh];
+    d.c.attester_bitfield_offs[row] = at[kApBits];
+    d.c.oblique_first[row] = at[kApElems];
+    d.c.aggregate_sig_first[row] = at[kApSigs];
+    for (uint64_t k = 0; k < r.sz[kApElems]; ++k)  // the element CSR, rebased
+      d.c.oblique_offs[at[kApElems] + k] = at[kApElemBytes] + (a.src.oblique_offs[r.lo[kApElems] + k] - r.lo[kApElemBytes]);
+#pragma unroll
+    for (int c = 0; c < 5; ++c)
+      if (len[c] <= a.long_bytes) copy_span(dp[c], sp[c], len[c]);
+  }
+#pragma unroll
+  for (int c = 0; c < 5; ++c) wave_copy_long(keep && len[c] > a.long_bytes, dp[c], sp[c], len[c]);
+}
+
+// ---- host side ---------------------------------------------------------------------------------
+uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
+uint64_t pad256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
+uint64_t scratch_bytes(uint64_t n) { return pad256((kApCols * tiles_of(n) + kApCols + sizeof(ApCall) / 8) * 8); }
+
+// Entries of buffer k of a set, and the width of one.
+uint64_t buf_entries(const uint64_t cap[kApCols], int k) {
+  switch (k) {
+    case 3: return cap[kApJbh] + 16;        // bytes columns: the digest kernels' 4 readable bytes and
+    case 5: return cap[kApSbh] + 16;        // the 16-byte pieces' room
+    case 7: return cap[kApBits] + 16;
+    case 9: return cap[kApElemBytes] + 16;
+    case 10: return cap[kApElems] + 1;
+    case 12: return cap[kApSigs] + 1;
+    case 4: case 6: case 8: case 11: case 13: return cap[kApRows] + 1;
+    default: return cap[kApRows];  // the scalars, committee, shard32
+  }
+}
+uint64_t buf_width(int k) { return (k == 3 || k == 5 || k == 7 || k == 9) ? 1 : k >= 14 ? 4 : 8; }
+
+ApDst set_dst(pz_att_pool* h, int s) {
+  ApDst d{};
+  pz::DevBuf* b = h->set[s];
+  d.c.slot = (uint64_t*)b[0].ptr, d.c.shard_id = (uint64_t*)b[1].ptr, d.c.justified_slot = (uint64_t*)b[2].ptr;
+  d.c.justified_block_hash = (uint8_t*)b[3].ptr, d.c.justified_block_hash_offs = (uint64_t*)b[4].ptr;
+  d.c.shard_block_hash = (uint8_t*)b[5].ptr, d.c.shard_block_hash_offs = (uint64_t*)b[6].ptr;
+  d.c.attester_bitfield = (uint8_t*)b[7].ptr, d.c.attester_bitfield_offs = (uint64_t*)b[8].ptr;
+  d.c.oblique_parent_hashes = (uint8_t*)b[9].ptr, d.c.oblique_offs = (uint64_t*)b[10].ptr;
+  d.c.oblique_first = (uint64_t*)b[11].ptr;
+  d.c.aggregate_sig = (uint64_t*)b[12].ptr, d.c.aggregate_sig_first = (uint64_t*)b[13].ptr;
+  d.committee = (uint32_t*)b[14].ptr, d.shard32 = (uint32_t*)b[15].ptr;
+  return d;
+}
+
+pz_attestation_cols as_cols(const ApDst& d) {
+  pz_attestation_cols c{};
+  c.slot = d.c.slot, c.shard_id = d.c.shard_id, c.justified_slot = d.c.justified_slot;
+  c.justified_block_hash = d.c.justified_block_hash, c.justified_block_hash_offs = d.c.justified_block_hash_offs;
+  c.shard_block_hash = d.c.shard_block_hash, c.shard_block_hash_offs = d.c.shard_block_hash_offs;
+  c.attester_bitfield = d.c.attester_bitfield, c.attester_bitfield_offs = d.c.attester_bitfield_offs;
+  c.oblique_parent_hashes = d.c.oblique_parent_hashes, c.oblique_offs = d.c.oblique_offs, c.oblique_first = d.c.oblique_first;
+  c.aggregate_sig = d.c.aggregate_sig, c.aggregate_sig_first = d.c.aggregate_sig_first;
+  return c;
+}
+
+int use_device(pz_att_pool* h) {
+  hipError_t e = hipSetDevice(h->device);
+  return e == hipSuccess ? PZ_OK : hip_fail(e, "hipSetDevice");
+}
+
+// What can be told about an append without reading a column; 1: nothing to do.
+int check_append(const pz_att_pool* h, const pz_attestation_cols* a, uint64_t n, const int32_t* status,
+                 const uint32_t* committee) {
+  if (!h) return fail(PZ_EINVAL, "attestation pool is null");
+  if (n == 0) return 1;
+  if (!a) return fail(PZ_EINVAL, "columns are null");
+  if (!status || !committee) return fail(PZ_EINVAL, "append: null status / committee");
+  if ((a->justified_block_hash_offs && !a->justified_block_hash) || (a->shard_block_hash_offs && !a->shard_block_hash) ||
+      (a->attester_bitfield_offs && !a->attester_bitfield) ||
+      (a->oblique_first && (!a->oblique_offs || !a->oblique_parent_hashes)) || (a->aggregate_sig_first && !a->aggregate_sig))
+    return fail(PZ_EINVAL, "offsets without their data column");
+  if (n >> 38) return fail(PZ_EINVAL, "more than 2^38 rows");  // (a tile per workgroup: the grid's limit)
+  return PZ_OK;
+}
+
+// The four launches on s.  scratch: tiles, totals, the call record.  ev (the A/B library's timed
+// entry; null in the product): five events, one before the first launch and one after each.
+int enqueue(pz_att_pool* h, ApArgs a, void* d_scratch, hipStream_t s, hipEvent_t* ev = nullptr) {
+  a.ntiles = tiles_of(a.n);
+  std::memcpy(a.cap, h->cap, sizeof a.cap);
+  a.counts = static_cast<uint64_t*>(h->words.ptr);
+  a.tiles = static_cast<uint64_t*>(d_scratch);
+  a.totals = a.tiles + kApCols * a.ntiles;
+  a.call = reinterpret_cast<ApCall*>(a.totals + kApCols);
+  a.long_bytes = g_long_bytes;
+  h->last = s;
+  hipError_t e;
+  auto stamp = [&](int k) {
+    if (ev) (void)hipEventRecord(ev[k], s);
+  };
+  stamp(0);
+  hipLaunchKernelGGL(pz_att_pool_size_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_att_pool_size_kernel");
+  stamp(1);
+  if ((e = launch_tile_scan(a.tiles, a.ntiles, (uint32_t)kApCols, a.totals, s)) != hipSuccess)
+    return hip_fail(e, "pz_unwire_scan_kernel");
+  stamp(2);
+  hipLaunchKernelGGL(pz_att_pool_commit_kernel, dim3(1), dim3(64), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_att_pool_commit_kernel");
+  stamp(3);
+  hipLaunchKernelGGL(pz_att_pool_write_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_att_pool_write_kernel");
+  stamp(4);
+  return PZ_OK;
+}
+
+ApArgs append_args(pz_att_pool* h, const pz_attestation_cols& a, uint64_t n, const int32_t* status,
+                   const uint32_t* committee, const uint8_t* take) {
+  ApArgs g;
+  std::memset(&g, 0, sizeof g);
+  g.src = a;
+  g.src_committee = committee;
+  g.status = status;
+  g.take = take;
+  g.n = n;
+  g.dst = set_dst(h, h->live);
+  return g;
+}
+
+ApArgs prune_args(pz_att_pool* h, uint64_t last_state_recalc) {
+  ApArgs g;
+  std::memset(&g, 0, sizeof g);
+  const ApDst from = set_dst(h, h->live);
+  g.src = as_cols(from);
+  g.src_committee = from.committee;
+  g.src_shard32 = from.shard32;
+  g.prune = 1;
+  g.last_state_recalc = last_state_recalc;
+  g.n = h->rows_ub;
+  g.dst = set_dst(h, h->live ^ 1);
+  return g;
+}
+
+// Waits for the last call and reads the counts and the sticky error word; the code to report.
+int settle(pz_att_pool* h, uint64_t counts[kApCols], int* sticky) {
+  hipError_t e = hipStreamSynchronize(h->last);
+  uint64_t w[kApCols + 1] = {};
+  if (e == hipSuccess) e = hipMemcpy(w, h->words.ptr, sizeof w, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return hip_fail(e, "attestation pool read");
+  std::memcpy(counts, w, kApCols * 8);
+  h->rows_ub = w[kApRows];
+  *sticky = (w[kApCols] & kApErrInverted) ? PZ_EINVAL : (w[kApCols] & kApErrCapacity) ? PZ_ERANGE : PZ_OK;
+  return PZ_OK;
+}
+
+int report(int sticky) {
+  if (sticky == PZ_EINVAL) return fail(PZ_EINVAL, "an appended row had an inverted range; it landed empty");
+  if (sticky == PZ_ERANGE) return fail(PZ_ERANGE, "an append needed more than the pool holds; it was dropped whole");
+  return PZ_OK;
+}
+
+// The largest entry of offs[0 .. n]: what a host column holds when its ranges start at 0.
+uint64_t span_end(const uint64_t* offs, uint64_t n) {
+  uint64_t m = 0;
+  for (uint64_t i = 0; offs && i <= n; ++i) m = std::max(m, offs[i]);
+  return m;
+}
+
+template <typename T>
+int down(T* host, const void* dev, uint64_t count) {
+  if (!host || !count) return PZ_OK;
+  hipError_t e = hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost);
+  return e == hipSuccess ? PZ_OK : hip_fail(e, "attestation pool read");
+}
+
+}  // namespace
+}  // namespace pz
+
+using namespace pz;
+
+extern "C" {
+
+int pz_att_pool_new(const uint64_t caps[7], int device, pz_att_pool** out) {
+  if (!out) return fail(PZ_EINVAL, "out is null");
+  *out = nullptr;
+  if (!caps) return fail(PZ_EINVAL, "caps is null");
+  if (caps[kApRows] == 0) return fail(PZ_EINVAL, "an attestation pool of zero rows");
+  for (int c = 0; c < kApCols; ++c)
+    if (caps[c] >> 40) return fail(PZ_EINVAL, "capacity %d is %llu: 2^40 or more", c, (unsigned long long)caps[c]);
+  DeviceCtx* dc;
+  int rc = device_ctx(device, &dc);
+  if (rc) return rc;
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  auto* h = new pz_att_pool();
+  h->device = device;
+  std::memcpy(h->cap, caps, sizeof h->cap);
+  for (int s = 0; s < 2 && !rc; ++s)
+    for (int k = 0; k < kSetBufs && !rc; ++k) {
+      const size_t bytes = (size_t)(buf_entries(caps, k) * buf_width(k));
+      if ((rc = h->set[s][k].reserve(bytes))) break;
+      if ((e = hipMemset(h->set[s][k].ptr, 0, bytes)) != hipSuccess) rc = hip_fail(e, "attestation pool init");
+    }
+  if (!rc) rc = h->words.reserve((kApCols + 1) * 8);
+  if (!rc) rc = h->scratch.reserve(scratch_bytes(caps[kApRows]));
+  if (!rc && (e = hipMemset(h->words.ptr, 0, (kApCols + 1) * 8)) != hipSuccess) rc = hip_fail(e, "attestation pool init");
+  if (!rc && (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "attestation pool init");
+  if (rc) {
+    delete h;
+    return rc;
+  }
+  *out = h;
+  return PZ_OK;
+}
+
+void pz_att_pool_free(pz_att_pool* h) { delete h; }
+
+uint64_t pz_att_pool_scratch_bytes(uint64_t n) { return scratch_bytes(n); }
+
+int pz_dev_att_pool_append(pz_att_pool* h, const pz_attestation_cols* a, uint64_t n, const int32_t* status,
+                           const uint32_t* committee, const uint8_t* take, void* d_scratch, void* stream) {
+  int rc = check_append(h, a, n, status, committee);
+  if (rc) return rc < 0 ? rc : PZ_OK;
+  if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15))
+    return fail(PZ_EINVAL, "d_scratch must be a 16-B aligned device pointer");
+  if ((rc = use_device(h))) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if ((rc = enqueue(h, append_args(h, *a, n, status, committee, take), d_scratch, static_cast<hipStream_t>(stream)))) return rc;
+  h->rows_ub = std::min(h->cap[kApRows], h->rows_ub + n);
+  return PZ_OK;
+}
+
+int pz_att_pool_append(pz_att_pool* h, const pz_attestation_cols* ha, uint64_t n, const int32_t* status,
+                       const uint32_t* committee, const uint8_t* take) {
+  int rc = check_append(h, ha, n, status, committee);
+  if (rc) return rc < 0 ? rc : PZ_OK;
+  if ((rc = use_device(h))) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceCtx* c;
+  if ((rc = device_ctx(h->device, &c))) return rc;
+  std::lock_guard<std::mutex> lc(c->mu);
+  Stager st{c, c->stream};
+  pz_attestation_cols d = *ha;
+  if (ha->slot) d.slot = st.up(ha->slot, n);
+  if (ha->shard_id) d.shard_id = st.up(ha->shard_id, n);
+  if (ha->justified_slot) d.justified_slot = st.up(ha->justified_slot, n);
+  if (ha->justified_block_hash_offs) {
+    d.justified_block_hash = st.up(ha->justified_block_hash, span_end(ha->justified_block_hash_offs, n));
+    d.justified_block_hash_offs = st.up(ha->justified_block_hash_offs, n + 1);
+  }
+  if (ha->shard_block_hash_offs) {
+    d.shard_block_hash = st.up(ha->shard_block_hash, span_end(ha->shard_block_hash_offs, n));
+    d.shard_block_hash_offs = st.up(ha->shard_block_hash_offs, n + 1);
+  }
+  if (ha->attester_bitfield_offs) {
+    d.attester_bitfield = st.up(ha->attester_bitfield, span_end(ha->attester_bitfield_offs, n));
+    d.attester_bitfield_offs = st.up(ha->attester_bitfield_offs, n + 1);
+  }
+  if (ha->oblique_first) {
+    const uint64_t ne = span_end(ha->oblique_first, n);
+    d.oblique_parent_hashes = st.up(ha->oblique_parent_hashes, span_end(ha->oblique_offs, ne));
+    d.oblique_offs = st.up(ha->oblique_offs, ne + 1);
+    d.oblique_first = st.up(ha->oblique_first, n + 1);
+  } else {
+    d.oblique_parent_hashes = nullptr, d.oblique_offs = nullptr;
+  }
+  if (ha->aggregate_sig_first) {
+    d.aggregate_sig = st.up(ha->aggregate_sig, span_end(ha->aggregate_sig_first, n));
+    d.aggregate_sig_first = st.up(ha->aggregate_sig_first, n + 1);
+  } else {
+    d.aggregate_sig = nullptr;
+  }
+  const int32_t* d_status = st.up(status, n);
+  const uint32_t* d_comm = st.up(committee, n);
+  const uint8_t* d_take = take ? st.up(take, n) : nullptr;
+  uint8_t* scr = st.up<uint8_t>(nullptr, scratch_bytes(n));
+  if (st.rc) return st.rc;
+  if ((rc = enqueue(h, append_args(h, d, n, d_status, d_comm, d_take), scr, st.s))) return rc;
+  h->rows_ub = std::min(h->cap[kApRows], h->rows_ub + n);
+  return st.sync();
+}
+
+int pz_dev_att_pool_prune(pz_att_pool* h, uint64_t last_state_recalc, void* stream) {
+  if (!h) return fail(PZ_EINVAL, "attestation pool is null");
+  int rc = use_device(h);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->rows_ub == 0) return PZ_OK;  // nothing was ever appended since the last exact count of 0
+  if ((rc = enqueue(h, prune_args(h, last_state_recalc), h->scratch.ptr, static_cast<hipStream_t>(stream)))) return rc;
+  h->live ^= 1;
+  return PZ_OK;
+}
+
+int pz_att_pool_counts(pz_att_pool* h, uint64_t counts[7]) {
+  if (!h || !counts) return fail(PZ_EINVAL, "attestation pool / counts is null");
+  int rc = use_device(h);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  int sticky;
+  if ((rc = settle(h, counts, &sticky))) return rc;
+  return report(sticky);
+}
+
+int pz_att_pool_view(pz_att_pool* h, pz_attestation_cols* cols, const uint32_t** committee, const uint32_t** shard32) {
+  if (!h) return fail(PZ_EINVAL, "attestation pool is null");
+  std::lock_guard<std::mutex> lk(h->mu);
+  const ApDst d = set_dst(h, h->live);
+  if (cols) *cols = as_cols(d);
+  if (committee) *committee = d.committee;
+  if (shard32) *shard32 = d.shard32;
+  return PZ_OK;
+}
+
+int pz_att_pool_read(pz_att_pool* h, const pz_attestation_cols_out* out, uint32_t* committee, const uint64_t caps[6]) {
+  if (!h || !out || !caps) return fail(PZ_EINVAL, "attestation pool / out / caps is null");
+  int rc = use_device(h);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  uint64_t n[kApCols];
+  int sticky;
+  if ((rc = settle(h, n, &sticky))) return rc;
+  static const char* const kWhat[6] = {"justified_block_hash", "shard_block_hash", "attester_bitfield",
+                                       "oblique elements",     "oblique bytes",    "aggregate_sig"};
+  for (int c = 0; c < 6; ++c)
+    if (n[c + 1] > caps[c])
+      return fail(PZ_ERANGE, "%s holds %llu, capacity %llu", kWhat[c], (unsigned long long)n[c + 1],
+                  (unsigned long long)caps[c]);
+  const ApDst d = set_dst(h, h->live);
+  const uint64_t r = n[kApRows];
+  if ((rc = down(out->slot, d.c.slot, r)) || (rc = down(out->shard_id, d.c.shard_id, r)) ||
+      (rc = down(out->justified_slot, d.c.justified_slot, r)) ||
+      (rc = down(out->justified_block_hash, d.c.justified_block_hash, n[kApJbh])) ||
+      (rc = down(out->justified_block_hash_offs, d.c.justified_block_hash_offs, r + 1)) ||
+      (rc = down(out->shard_block_hash, d.c.shard_block_hash, n[kApSbh])) ||
+      (rc = down(out->shard_block_hash_offs, d.c.shard_block_hash_offs, r + 1)) ||
+      (rc = down(out->attester_bitfield, d.c.attester_bitfield, n[kApBits])) ||
+      (rc = down(out->attester_bitfield_offs, d.c.attester_bitfield_offs, r + 1)) ||
+      (rc = down(out->oblique_parent_hashes, d.c.oblique_parent_hashes, n[kApElemBytes])) ||
+      (rc = down(out->oblique_offs, d.c.oblique_offs, n[kApElems] + 1)) ||
+      (rc = down(out->oblique_first, d.c.oblique_first, r + 1)) ||
+      (rc = down(out->aggregate_sig, d.c.aggregate_sig, n[kApSigs])) ||
+      (rc = down(out->aggregate_sig_first, d.c.aggregate_sig_first, r + 1)) || (rc = down(committee, d.committee, r)))
+    return rc;
+  return report(sticky);
+}
+
+int pz_att_pool_shard_block_hashes(pz_att_pool* h, const uint32_t* rows, uint64_t nrows, uint8_t* out, uint64_t cap,
+                                   uint64_t* offs) {
+  if (!h || !offs || (nrows && !rows)) return fail(PZ_EINVAL, "attestation pool / rows / offs is null");
+  int rc = use_device(h);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  uint64_t n[kApCols];
+  int sticky;
+  if ((rc = settle(h, n, &sticky))) return rc;
+  const ApDst d = set_dst(h, h->live);
+  std::vector<uint64_t> so(n[kApRows] + 1);
+  std::vector<uint8_t> sb(n[kApSbh]);
+  if ((rc = down(so.data(), d.c.shard_block_hash_offs, so.size())) || (rc = down(sb.data(), d.c.shard_block_hash, sb.size())))
+    return rc;
+  offs[0] = 0;
+  for (uint64_t k = 0; k < nrows; ++k) {
+    if (rows[k] >= n[kApRows])
+      return fail(PZ_EINDEX, "row %u of a pool of %llu rows", rows[k], (unsigned long long)n[kApRows]);
+    offs[k + 1] = offs[k] + (so[rows[k] + 1] - so[rows[k]]);
+  }
+  if (offs[nrows] > cap)
+    return fail(PZ_ERANGE, "the hashes take %llu bytes, capacity %llu", (unsigned long long)offs[nrows], (unsigned long long)cap);
+  for (uint64_t k = 0; k < nrows; ++k)
+    if (offs[k + 1] > offs[k]) std::memcpy(out + offs[k], sb.data() + so[rows[k]], offs[k + 1] - offs[k]);
+  return PZ_OK;
+}
+
+#ifdef PZ_AB_BUILD
+// (tools/attpool_probe.py) The long-range threshold of the write launch (0: the product's); returns
+// the previous one.  At least 16: the wave copy's tail is the range's last 16 bytes.
+uint64_t pz_debug_att_pool_long_bytes(uint64_t bytes) {
+  const uint64_t old = g_long_bytes;
+  g_long_bytes = bytes == 0 ? kApLongBytes : std::max<uint64_t>(bytes, 16);
+  return old;
+}
+
+// (tools/attpool_probe.py) pz_dev_att_pool_append (a non-null a) or pz_dev_att_pool_prune (a null)
+// with one event pair per launch; synchronises and returns the four launches' milliseconds (size,
+// scan, commit, write) in ms[0..4).
+int pz_debug_att_pool_timed(pz_att_pool* h, const pz_attestation_cols* a, uint64_t n, const int32_t* status,
+                            const uint32_t* committee, const uint8_t* take, uint64_t last_state_recalc, void* d_scratch,
+                            void* stream, float ms[4]) {
+  if (!h || !ms) return fail(PZ_EINVAL, "null pointer");
+  int rc = use_device(h);
+  if (rc) return rc;
+  if (a && ((rc = check_append(h, a, n, status, committee)) || !d_scratch)) return rc < 0 ? rc : fail(PZ_EINVAL, "nothing to time");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!a && h->rows_ub == 0) return fail(PZ_EINVAL, "nothing to time");
+  hipEvent_t ev[5];
+  for (auto& x : ev)
+    if (hipEventCreate(&x) != hipSuccess) return fail(PZ_EDEVICE, "hipEventCreate");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (a) {
+    rc = enqueue(h, append_args(h, *a, n, status, committee, take), d_scratch, s, ev);
+    if (!rc) h->rows_ub = std::min(h->cap[kApRows], h->rows_ub + n);
+  } else {
+    rc = enqueue(h, prune_args(h, last_state_recalc), h->scratch.ptr, s, ev);
+    if (!rc) h->live ^= 1;
+  }
+  hipError_t e = hipStreamSynchronize(s);
+  for (int k = 0; k < 4 && !rc && e == hipSuccess; ++k) e = hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+  for (auto& x : ev) (void)hipEventDestroy(x);
+  if (rc) return rc;
+  return e == hipSuccess ? PZ_OK : hip_fail(e, "timed attestation pool call");
+}
+#endif
+
+}  // extern "C"

@@ -26,91 +26,12 @@
 
 #include "proto3_canon.h"
 #include "runtime.h"
+#include "tile_scan.h"
 
 namespace pz {
 namespace {
 
-constexpr int kTile = 256, kTileWaves = kTile / 64;
-constexpr int kScanThreads = 1024;
 constexpr int kAttCols = 7;  // d_totals' order: three bytes fields, elements, element bytes, sig values, bad records
-
-typedef __attribute__((address_space(1))) uint8_t gbyte;
-
-// 16-byte unaligned pieces, the last one overlapping the one before it with the same bytes:
-// every load and store lies inside [0, len) (gfx950 runs unaligned global accesses); a span under
-// 16 bytes goes byte by byte.
-__device__ __forceinline__ void copy16(gbyte* dst, const gbyte* src) {
-  uint4 v;
-  __builtin_memcpy(&v, src, 16);
-  __builtin_memcpy(dst, &v, 16);
-}
-
-__device__ __forceinline__ void copy_span(uint8_t* dst, const uint8_t* src, uint64_t len) {
-  gbyte* o = reinterpret_cast<gbyte*>((uintptr_t)dst);
-  const gbyte* s = reinterpret_cast<const gbyte*>((uintptr_t)src);
-  if (len >= 16) {
-    uint64_t k = 0;
-    for (; k + 16 <= len; k += 16) copy16(o + k, s + k);
-    if (k < len) copy16(o + len - 16, s + len - 16);
-  } else {
-    for (uint64_t k = 0; k < len; ++k) o[k] = s[k];
-  }
-}
-
-__device__ __forceinline__ uint64_t wsum(uint64_t x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  return x;
-}
-
-// Inclusive scan over the wave.
-__device__ __forceinline__ uint64_t wscan(uint64_t x) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  return x;
-}
-
-// The tile's sums of N values per lane, to tiles[c * ntiles + blockIdx.x].
-template <int N>
-__device__ __forceinline__ void tile_sums(const uint64_t (&v)[N], uint64_t* tiles, uint64_t ntiles) {
-  __shared__ uint64_t s_sum[N][kTileWaves];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int c = 0; c < N; ++c) {
-    const uint64_t t = wsum(v[c]);
-    if (lane == 0) s_sum[c][w] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < N) {
-    uint64_t t = 0;
-    for (int k = 0; k < kTileWaves; ++k) t += s_sum[threadIdx.x][k];
-    tiles[threadIdx.x * ntiles + blockIdx.x] = t;
-  }
-}
-
-// Each lane's exclusive prefix of N values within the tile (every lane of the workgroup calls).
-template <int N>
-__device__ __forceinline__ void tile_excl(const uint64_t (&v)[N], uint64_t (&ex)[N]) {
-  __shared__ uint64_t s_inc[N][kTileWaves];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint64_t inc[N];
-#pragma unroll
-  for (int c = 0; c < N; ++c) {
-    inc[c] = wscan(v[c]);
-    if (lane == 63) s_inc[c][w] = inc[c];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < N; ++c) {
-    uint64_t before = 0;
-    for (int k = 0; k < kTileWaves; ++k) before += k < w ? s_inc[c][k] : 0;
-    ex[c] = before + inc[c] - v[c];
-  }
-}
 
 // Launch 2 of both decodes: column c's tile sums tiles[c * ntiles ..] become the tiles'
 // exclusive bases, totals[c] the column's sum.  One workgroup; a column is walked kScanThreads
@@ -304,9 +225,7 @@ hipError_t launch_unwire_att(AttArgs a, uint64_t* totals, void* scratch, hipStre
   a.tiles = a.sizes + (kAttCols - 1) * a.n;
   hipLaunchKernelGGL(pz_unwire_att_size_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(pz_unwire_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, a.tiles, a.ntiles, (uint32_t)kAttCols,
-                     totals);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = launch_tile_scan(a.tiles, a.ntiles, (uint32_t)kAttCols, totals, s)) != hipSuccess) return e;
   hipLaunchKernelGGL(pz_unwire_att_write_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
   return hipGetLastError();
 }
@@ -438,13 +357,18 @@ hipError_t launch_unwire_blocks(BlockArgs a, uint64_t* natt, void* scratch, hipS
   a.tiles = a.counts + a.n;
   hipLaunchKernelGGL(pz_unwire_block_size_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(pz_unwire_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, a.tiles, a.ntiles, 1u, natt);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = launch_tile_scan(a.tiles, a.ntiles, 1u, natt, s)) != hipSuccess) return e;
   hipLaunchKernelGGL(pz_unwire_block_write_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
   return hipGetLastError();
 }
 
 }  // namespace
+
+hipError_t launch_tile_scan(uint64_t* tiles, uint64_t ntiles, uint32_t ncols, uint64_t* totals, hipStream_t s) {
+  hipLaunchKernelGGL(pz_unwire_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, tiles, ntiles, ncols, totals);
+  return hipGetLastError();
+}
+
 }  // namespace pz
 
 using namespace pz;

@@ -1,0 +1,263 @@
+"""ActiveState.PendingAttestations resident on one device -- Python face of ``pz_att_pool``
+(prysm_amd/csrc/attpool.hip, include/prysm_hip.h).
+
+The attestations a block contributes (processedAttestations, blockchain/service.go:280-301) become
+pending attestations (computeNewActiveState, core.go:223-237) and feed the cycle transition
+(core.go:433-457).  ``DevicePendingAttestations`` holds them as device columns: it is appended to
+from the decoder's columns and the checks' outputs where they lie, pruned by slot, and read in
+place -- as the epoch kernels' attestation inputs, as the columns ``pz_dev_wire_attestations``
+encodes into the stored ActiveState's field 1, and as the crosslink winners' ShardBlockHash.
+``RecalcState`` is the CrystallizedState side of ``blockchain.state_recalc_device``.
+"""
+import numpy as np
+
+from prysm_amd import _lib, pb, wire
+from prysm_amd._lib import lib
+
+CAPS = ("rows", "justified_block_hash", "shard_block_hash", "attester_bitfield", "oblique_elements", "oblique_bytes",
+        "aggregate_sig")  # pz_att_pool_new's caps[7] / pz_att_pool_counts' counts[7]
+_BYTES = ("justified_block_hash", "shard_block_hash", "attester_bitfield", "oblique_parent_hashes")
+_STICKY = (_lib.PZ_EINVAL, _lib.PZ_ERANGE)
+
+
+class _Raw:
+    """A device address as something ``torch.as_tensor`` can wrap without a copy."""
+
+    def __init__(self, ptr, nbytes):
+        self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+
+class DevicePendingAttestations:
+    """``caps``: the seven capacities (``CAPS``' order), fixed for the pool's lifetime.  A call that
+    would exceed one changes nothing (PZ_ERANGE, sticky); a kept row with an inverted range lands
+    empty (PZ_EINVAL, sticky).  Every read raises the sticky error; ``strict=False`` returns what the
+    pool holds regardless."""
+
+    def __init__(self, caps, device=0):
+        self.caps = np.ascontiguousarray(caps, dtype=np.uint64)
+        assert self.caps.shape == (7,)
+        self._h = _lib.ctypes.c_void_p()
+        lib.call("pz_att_pool_new", self.caps.ctypes.data, device, _lib.ctypes.byref(self._h))
+        self.device = device
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            lib.dll.pz_att_pool_free(h)
+            self._h = None
+
+    def _stream(self):
+        import torch
+
+        return _lib.ctypes.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+
+    # ---- writes ------------------------------------------------------------------------------
+    def append_columns(self, cols, n, status, committee, take=None):
+        """Appends the rows of ``cols`` (torch device tensors keyed as ``wire.ATT_COLS``, e.g. from
+        ``wire.unwire_attestations_device``; a missing or None column follows pz_attestation_cols'
+        NULL rules) whose ``status`` (int32) is PZ_ATT_PROCESSED and whose ``take`` (uint8,
+        optional) is not 0; ``committee`` (int32): the checks' committee ids.  On the current
+        stream, asynchronous (``pz_dev_att_pool_append``)."""
+        import torch
+
+        dev = status.device
+        one = torch.zeros(1, dtype=torch.uint8, device=dev)  # (a bytes column with no byte still needs an address)
+        ptrs = []
+        for k in wire.ATT_COLS:
+            v = cols.get(k)
+            if v is not None and not v.numel() and (k in _BYTES or k == "aggregate_sig"):
+                v = one
+            ptrs.append(v.data_ptr() if v is not None and v.numel() else None)
+        c = _lib.AttestationCols(*ptrs)
+        scratch = torch.empty(max(int(lib.dll.pz_att_pool_scratch_bytes(n)), 16), dtype=torch.uint8, device=dev)
+        p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        lib.call("pz_dev_att_pool_append", self._h, _lib.ctypes.byref(c), n, p(status), p(committee), p(take),
+                 scratch.data_ptr(), self._stream())
+
+    def append_host(self, cols, n, status, committee, take=None):
+        """The same append over host arrays (numpy; ``pz_att_pool_append``, synchronous)."""
+        keep = {k: np.ascontiguousarray(cols[k]) for k in wire.ATT_COLS if cols.get(k) is not None}
+        one = np.zeros(1, dtype=np.uint8)
+        for k in _BYTES:
+            if k in keep and not keep[k].size:
+                keep[k] = one
+        if "aggregate_sig" in keep and not keep["aggregate_sig"].size:
+            keep["aggregate_sig"] = np.zeros(1, dtype=np.uint64)
+        c = _lib.AttestationCols(**{k: v.ctypes.data for k, v in keep.items()})
+        status = np.ascontiguousarray(status, dtype=np.int32)
+        committee = np.ascontiguousarray(committee, dtype=np.uint32)
+        take = None if take is None else np.ascontiguousarray(take, dtype=np.uint8)
+        lib.call("pz_att_pool_append", self._h, _lib.ctypes.byref(c), n, _lib.ptr(status), _lib.ptr(committee),
+                 _lib.ptr(take))
+
+    def prune(self, last_state_recalc):
+        """stateRecalc's filter (core.go:444-450): keeps the rows with ``slot > last_state_recalc``.
+        On the current stream, asynchronous."""
+        lib.call("pz_dev_att_pool_prune", self._h, int(last_state_recalc), self._stream())
+
+    # ---- reads -------------------------------------------------------------------------------
+    def _rc(self, rc, strict):
+        if rc != _lib.PZ_OK and (strict or rc not in _STICKY):
+            raise _lib.PzError(rc, lib.dll.pz_last_error().decode())
+
+    def counts(self, strict=True):
+        """The seven counts (``CAPS``' order) as a uint64 array; waits for the last call."""
+        out = np.zeros(7, dtype=np.uint64)
+        self._rc(lib.dll.pz_att_pool_counts(self._h, out.ctypes.data), strict)
+        return out
+
+    def __len__(self):
+        return int(self.counts(strict=False)[0])
+
+    def view(self):
+        """``(AttestationCols, committee, shard32)``: device addresses into the live buffer set,
+        valid until the next prune."""
+        c = _lib.AttestationCols()
+        comm, s32 = _lib.ctypes.c_void_p(), _lib.ctypes.c_void_p()
+        lib.call("pz_att_pool_view", self._h, _lib.ctypes.byref(c), _lib.ctypes.byref(comm), _lib.ctypes.byref(s32))
+        return c, comm.value, s32.value
+
+    def raw_columns(self):
+        """The live buffer set's bytes columns and ``aggregate_sig`` at their full capacities, as
+        uint8 torch tensors over the pool's own memory (no copy; tests write canaries through them)."""
+        import torch
+
+        c, _, _ = self.view()
+        cap = dict(zip(CAPS, (int(x) for x in self.caps)))
+        size = {"justified_block_hash": cap["justified_block_hash"], "shard_block_hash": cap["shard_block_hash"],
+                "attester_bitfield": cap["attester_bitfield"], "oblique_parent_hashes": cap["oblique_bytes"],
+                "aggregate_sig": 8 * cap["aggregate_sig"]}
+        dev = torch.device("cuda", self.device)
+        return {k: torch.as_tensor(_Raw(getattr(c, k), nb), device=dev) for k, nb in size.items() if nb}
+
+    def shard32(self):
+        """The ``shard32`` column (ShardId saturated to UINT32_MAX: the epoch kernels' ``att_shard``)
+        as a uint32 array."""
+        import torch
+
+        rows = len(self)
+        if not rows:
+            return np.zeros(0, dtype=np.uint32)
+        _, _, s32 = self.view()
+        t = torch.as_tensor(_Raw(s32, 4 * rows), device=torch.device("cuda", self.device))
+        return t.cpu().numpy().view(np.uint32)
+
+    def columns(self, strict=True):
+        """Everything the pool holds as numpy arrays keyed as ``wire.ATT_COLS``, plus ``committee``
+        (``pz_att_pool_read``)."""
+        n = self.counts(strict=False)
+        rows, jb, sb, bf, ne, eb, ns = (int(x) for x in n)
+        size = {k: rows for k in wire.ATT_COLS}
+        size.update({k: rows + 1 for k in wire.ATT_COLS if k.endswith("_offs") or k.endswith("_first")})
+        size.update(justified_block_hash=jb, shard_block_hash=sb, attester_bitfield=bf, oblique_parent_hashes=eb,
+                    oblique_offs=ne + 1, aggregate_sig=ns)
+        cols = {k: np.zeros(max(size[k], 1), dtype=np.uint8 if k in _BYTES else np.uint64) for k in wire.ATT_COLS}
+        committee = np.zeros(max(rows, 1), dtype=np.uint32)
+        out = _lib.AttestationColsOut(*[cols[k].ctypes.data for k in wire.ATT_COLS], None, None, None)
+        caps = np.array([jb, sb, bf, ne, eb, ns], dtype=np.uint64)
+        self._rc(lib.dll.pz_att_pool_read(self._h, _lib.ctypes.byref(out), committee.ctypes.data, caps.ctypes.data), strict)
+        res = {k: v[:size[k]] for k, v in cols.items()}
+        res["committee"] = committee[:rows]
+        return res
+
+    def records(self, strict=True):
+        """PendingAttestations() as ``pb.AttestationRecord``s, in order."""
+        c = self.columns(strict)
+        span = lambda k, i: c[k][int(c[k + "_offs"][i]):int(c[k + "_offs"][i + 1])].tobytes()  # noqa: E731
+        oo, data = c["oblique_offs"], c["oblique_parent_hashes"]
+        out = []
+        for i in range(len(c["slot"])):
+            e0, e1 = int(c["oblique_first"][i]), int(c["oblique_first"][i + 1])
+            s0, s1 = int(c["aggregate_sig_first"][i]), int(c["aggregate_sig_first"][i + 1])
+            out.append(pb.AttestationRecord(
+                slot=int(c["slot"][i]), shard_id=int(c["shard_id"][i]), justified_slot=int(c["justified_slot"][i]),
+                justified_block_hash=span("justified_block_hash", i), shard_block_hash=span("shard_block_hash", i),
+                attester_bitfield=span("attester_bitfield", i),
+                oblique_parent_hashes=[data[int(oo[e]):int(oo[e + 1])].tobytes() for e in range(e0, e1)],
+                aggregate_sig=[int(x) for x in c["aggregate_sig"][s0:s1]]))
+        return out
+
+    def wire(self, field_num=1):
+        """The pool's view encoded where it lies by ``pz_dev_wire_attestations`` on the current
+        stream: with ``field_num=1`` the leading bytes of the stored ActiveState
+        (types/state.go:141).  Returns ``(bytes, offsets[n+1] uint64)``."""
+        import torch
+
+        rows, jb, sb, bf, ne, eb, ns = (int(x) for x in self.counts())
+        if not rows:
+            return b"", np.zeros(1, dtype=np.uint64)
+        dev = torch.device("cuda", self.device)
+        c, _, _ = self.view()
+        out = torch.empty(max(int(lib.dll.pz_wire_attestations_bound(rows, jb + sb + bf + eb, ne, ns)), 1),
+                          dtype=torch.uint8, device=dev)
+        offs = torch.empty(rows + 1, dtype=torch.int64, device=dev)
+        scr = torch.empty(max(int(lib.dll.pz_wire_attestations_scratch_bytes(rows)), 16), dtype=torch.uint8, device=dev)
+        lib.call("pz_dev_wire_attestations", _lib.ctypes.byref(c), rows, field_num, out.data_ptr(), offs.data_ptr(),
+                 scr.data_ptr(), self._stream())
+        offs = offs.cpu().numpy().view(np.uint64)
+        return out[:int(offs[-1])].cpu().numpy().tobytes(), offs
+
+    def shard_block_hashes(self, rows):
+        """ShardBlockHash of the named rows, a list of byte strings: what a crosslink winner writes
+        into its record (core.go:550-554)."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        offs = np.zeros(len(rows) + 1, dtype=np.uint64)
+        out = np.zeros(1, dtype=np.uint8)
+        rc = lib.dll.pz_att_pool_shard_block_hashes(self._h, _lib.ptr(rows), len(rows), None, 0, offs.ctypes.data)
+        if rc == _lib.PZ_ERANGE:  # (offs is filled: the size to come back with)
+            out = np.zeros(int(offs[-1]), dtype=np.uint8)
+            rc = lib.dll.pz_att_pool_shard_block_hashes(self._h, _lib.ptr(rows), len(rows), out.ctypes.data, out.size,
+                                                        offs.ctypes.data)
+        self._rc(rc, True)
+        return [out[int(offs[k]):int(offs[k + 1])].tobytes() for k in range(len(rows))]
+
+    def epoch_batch(self, batch=None):
+        """Fills the attestation side of an ``_lib.EpochBatch`` (``natt``, ``bits``, ``boffs``,
+        ``max_inst_bytes``, ``att_comm``, ``att_shard``) from the view and the counts, for
+        ``ninst = 1``; the caller fills the validators, committees, records and outputs (``vote`` and
+        ``total`` hold ``natt`` entries).  Returns the batch."""
+        b = _lib.EpochBatch() if batch is None else batch
+        n = self.counts()
+        c, comm, s32 = self.view()
+        b.ninst = 1
+        b.natt = int(n[0])
+        b.bits, b.boffs = c.attester_bitfield, c.attester_bitfield_offs
+        b.max_inst_bytes = int(n[3])
+        b.att_comm, b.att_shard = comm, s32
+        return b
+
+
+class RecalcState:
+    """The CrystallizedState ``blockchain.state_recalc_device`` advances: ``balance``, ``start`` and
+    ``end`` (the validators' Balance / StartDynasty / EndDynasty) as int64 device tensors, the
+    committees as a device CSR (``members`` int32, ``coffs`` int64), the host scalars and the
+    crosslink records (``pb.CrosslinkRecord``)."""
+
+    def __init__(self, balance, start_dynasty, end_dynasty, members, coffs, crosslink_records, *, last_state_recalc=0,
+                 justified_streak=0, last_justified_slot=0, last_finalized_slot=0, current_dynasty=1, total_deposits=0,
+                 device=0):
+        import torch
+
+        from prysm_amd.blockchain import _to_device
+
+        dev = torch.device("cuda", device)
+        u64 = lambda a: _to_device(np.ascontiguousarray(a, dtype=np.uint64), dev)  # noqa: E731
+        self.device = device
+        self.balance, self.start, self.end = u64(balance), u64(start_dynasty), u64(end_dynasty)
+        members = np.ascontiguousarray(members, dtype=np.uint32)
+        self.members = _to_device(members if members.size else np.zeros(1, np.uint32), dev)
+        self.coffs = u64(coffs)
+        self.crosslink_records = [pb.CrosslinkRecord(r.dynasty, bytes(r.blockhash), r.slot) for r in crosslink_records]
+        self.last_state_recalc, self.justified_streak = int(last_state_recalc), int(justified_streak)
+        self.last_justified_slot, self.last_finalized_slot = int(last_justified_slot), int(last_finalized_slot)
+        self.current_dynasty, self.total_deposits = int(current_dynasty), int(total_deposits)
+
+    @property
+    def nval(self):
+        return int(self.balance.numel())
+
+    def balances(self):
+        return self.balance.cpu().numpy().view(np.uint64)
+
+
+__all__ = ["DevicePendingAttestations", "RecalcState", "CAPS"]
