@@ -834,6 +834,20 @@ int pz_vote_cache_read(pz_vote_cache* cache, uint8_t* hashes, uint64_t* totals, 
 /* VoterIndices of one hash as a bitmap (ceil(nval / 32) u32 words, bit v & 31 of word v >> 5;
  * zeros when absent) and *present = the map has the entry.  Same waiting and errors as read. */
 int pz_vote_cache_voters(pz_vote_cache* cache, const uint8_t hash[32], uint32_t* words, int* present);
+/* `if _, ok := blockVoteCache[blockHash]` and .VoteTotalDeposit, core.go:414-418, for n hashes
+ * (BytesToHash-normalised, n x 32 bytes) on the device: d_totals[q] is the entry's VoteTotalDeposit,
+ * 0 when the map has none; d_slots[q] (optional) its slot id, 0xFFFFFFFF when absent.  One launch
+ * on the caller's stream, a lane per query walking the table above with plain loads: the caller
+ * orders it after the cache's earlier calls (one stream, or its own events) and no call of the
+ * cache may run beside it.  Reports no sticky error (read and voters do).  n == 0 launches nothing.
+ * PZ_EINVAL, before any launch: a NULL cache; with n > 0 a NULL d_hashes or d_totals, or a
+ * d_hashes that is not 16-byte aligned. */
+int pz_dev_vote_cache_lookup(pz_vote_cache* cache, const uint8_t* d_hashes, uint64_t n, uint64_t* d_totals,
+                             uint32_t* d_slots /* optional */, void* stream);
+/* The same lookup (core.go:414-418) over host pointers (any alignment), synchronous; waits for the
+ * stream of the cache's last call first. */
+int pz_vote_cache_lookup(pz_vote_cache* cache, const uint8_t* hashes, uint64_t n, uint64_t* totals,
+                         uint32_t* slots /* optional */);
 
 /* ---- R: ActiveState.PendingAttestations resident on the device --------------------------------
  * The attestations a block contributes (processedAttestations, blockchain/service.go:280-301)
@@ -903,6 +917,78 @@ int pz_att_pool_read(pz_att_pool* pool, const pz_attestation_cols_out* out, uint
  * bytes exceed cap. */
 int pz_att_pool_shard_block_hashes(pz_att_pool* pool, const uint32_t* rows, uint64_t nrows, uint8_t* out, uint64_t cap,
                                    uint64_t* offs);
+
+/* ---- R: stateRecalc over the resident pool and vote cache -----------------------------------------
+ * The cycle transition (stateRecalc, blockchain/core.go:398-497) as one call: the justification
+ * loop over the vote cache (core.go:411-431), processCrosslinks, CalculateRewards and the
+ * next-cycle balance over the pending-attestation pool (core.go:433-464), the new crosslink
+ * records (core.go:549-555), the new CrystallizedState's scalars (core.go:467-478) and the pool's
+ * prune (core.go:444-450).  pz_recalc_state owns, on one device, the CrystallizedState's side:
+ * scalars[PZ_RS_COUNT] (u64, the indices below, the rest zero), the crosslink records as columns
+ * (rec_dynasty, rec_slot u64; rec_hash at hash_stride bytes a record with rec_hash_len u32), the
+ * last call's winners and a sticky error word.  hash_stride is fixed at creation, a multiple of 16
+ * in [32, 256].  The validators (balance, start, end) and the committee CSR stay the caller's
+ * device arrays.  Single device: the epoch runs with pop_world = 1 and no co_index.
+ *
+ * One call is, on the caller's stream (no workgroup waits for another):
+ *   1 a fit check over the pool's rows and the call's ONE wait, for the pool's seven counts, the
+ *     handle's lastStateRecalc and the check's flag (pz_epoch_batch.natt, max_inst_bytes and the
+ *     prune's bound are host values).  A pending ShardBlockHash longer than hash_stride -- on any
+ *     row: any could win -- is PZ_ERANGE and nothing changes.  The check can only refuse.
+ *   2 the justification: one wave, lane i looks RecentBlockHashes()[i] up in the cache (0 with a
+ *     NULL cache), 3 * total >= 2 * TotalDeposits mod 2^64, and the loop of core.go:411-431 runs
+ *     over the ballot, slot = lastStateRecalc - 64 + i and slot - 64 wrapping as Go's do.
+ *   3 pz_dev_epoch_count then pz_dev_epoch_finish, one instance over pz_att_pool_view; dynasty,
+ *     total_deposit and rec_dynasty are the handle's own memory.
+ *   4 the commit.  Where the reference panics -- scal[PZ_SCAL_ERR_XL] != 0, or pop * 32 * 3 >=
+ *     2 * TotalDeposits mod 2^64 with PZ_SCAL_NACT > 0 and PZ_SCAL_ERR_RWD != 0 -- the sticky
+ *     PZ_EINDEX bit is set, nothing of the handle is written, the balances are untouched (the
+ *     epoch kernels' contract) and the pool's contents are unspecified.  Otherwise every record
+ *     with a winner becomes {CurrentDynasty, block_slot, the winning row's ShardBlockHash}, and
+ *     the scalars become lastStateRecalc + 64, the loop's three values, TotalDeposits =
+ *     scal[PZ_SCAL_NEXT_BAL] and CurrentDynasty = 0 (the reference's new state leaves it unset).
+ *   5 pz_dev_att_pool_prune(pool, lastStateRecalc).
+ * Calls on the three objects are ordered by the caller (one stream, or its own events).
+ * Thread-safe per handle. */
+#define PZ_RS_LAST_STATE_RECALC   0
+#define PZ_RS_JUSTIFIED_STREAK    1
+#define PZ_RS_LAST_JUSTIFIED_SLOT 2
+#define PZ_RS_LAST_FINALIZED_SLOT 3
+#define PZ_RS_CURRENT_DYNASTY     4
+#define PZ_RS_TOTAL_DEPOSITS      5
+#define PZ_RS_COUNT               8
+typedef struct pz_recalc_state pz_recalc_state;
+/* NewCrystallizedState (types/state.go:34): its scalars and CrosslinkRecords from host pointers;
+ * the records' hashes are CSR (rec_hash_offs holds nrec + 1 entries).  nrec may be 0.  PZ_EINVAL: a
+ * bad hash_stride, NULL scalars, NULL columns with nrec > 0; PZ_ERANGE: a record's hash is longer
+ * than hash_stride. */
+int  pz_recalc_state_new(uint32_t nrec, uint32_t hash_stride, const uint64_t scalars[PZ_RS_COUNT],
+                         const uint64_t* rec_dynasty, const uint64_t* rec_slot, const uint8_t* rec_hash,
+                         const uint64_t* rec_hash_offs, int device, pz_recalc_state** out);
+void pz_recalc_state_free(pz_recalc_state* st);
+/* Host download of the scalars, the records (rec_hash: nrec x hash_stride bytes, zero behind each
+ * record's rec_hash_len) and the last call's winner[nrec] (one pool row per record before the
+ * prune, 0xFFFFFFFF: none; core.go:549-555); any output may be NULL.  Waits for the last call's
+ * stream.  The sticky error comes first (PZ_EINDEX where stateRecalc panics); the outputs are
+ * filled all the same and hold the state before the panicking call. */
+int  pz_recalc_state_read(pz_recalc_state* st, uint64_t scalars[PZ_RS_COUNT], uint64_t* rec_dynasty, uint64_t* rec_slot,
+                          uint8_t* rec_hash, uint32_t* rec_hash_len, uint32_t* winner);
+typedef struct pz_recalc_batch {           /* device pointers */
+  uint64_t nval; uint64_t* balance; const uint64_t *start, *end;
+  const uint32_t* members; const uint64_t* coffs;   /* committees, CSR, full */
+  const uint8_t* recent; uint64_t n_recent;         /* RecentBlockHashes(), BytesToHash-normalised, 16-B aligned */
+  uint64_t block_slot;                              /* the transition block's SlotNumber */
+} pz_recalc_batch;
+/* The scratch one call needs (no reference counterpart); rows_cap: the pool's row capacity. */
+uint64_t pz_state_recalc_scratch_bytes(uint64_t nval, uint64_t rows_cap, uint32_t nrec);
+/* stateRecalc, core.go:398-497, as above.  cache may be NULL (no entry: every total 0).
+ * PZ_EINDEX before any launch, nothing changed, when n_recent < 64 (the panic of core.go:413).
+ * PZ_EINVAL, before any launch: a NULL state, pool, batch, scratch or batch member; recent or
+ * d_scratch not 16-byte aligned; nval different from the cache's; objects on different devices.
+ * PZ_ERANGE from the fit check, nothing changed.  A panic the kernels find is sticky and reported
+ * by pz_recalc_state_read, not here. */
+int pz_dev_state_recalc(pz_recalc_state* st, pz_att_pool* pool, pz_vote_cache* cache /* NULL: no entry */,
+                        const pz_recalc_batch* b, void* d_scratch, void* stream);
 
 typedef struct pz_block_result {
   uint8_t hash[32];      /* Block.Hash() */

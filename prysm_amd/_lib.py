@@ -115,6 +115,8 @@ SIGNATURES = {
     "pz_vote_cache_tally": [vp, vp],
     "pz_vote_cache_read": [vp, vp, vp, u64, c_u64p],
     "pz_vote_cache_voters": [vp, vp, vp, c_intp],
+    "pz_dev_vote_cache_lookup": [vp, vp, u64, vp, vp, vp],
+    "pz_vote_cache_lookup": [vp, vp, u64, vp, vp],
     "pz_att_pool_new": [vp, ctypes.c_int, vp],
     "pz_att_pool_free": [vp],
     "pz_att_pool_scratch_bytes": [u64],
@@ -125,6 +127,11 @@ SIGNATURES = {
     "pz_att_pool_view": [vp, vp, vp, vp],
     "pz_att_pool_read": [vp, vp, vp, vp],
     "pz_att_pool_shard_block_hashes": [vp, vp, u64, vp, u64, vp],
+    "pz_recalc_state_new": [u32, u32, vp, vp, vp, vp, vp, ctypes.c_int, vp],
+    "pz_recalc_state_free": [vp],
+    "pz_recalc_state_read": [vp, vp, vp, vp, vp, vp, vp],
+    "pz_state_recalc_scratch_bytes": [u64, u64, u32],
+    "pz_dev_state_recalc": [vp, vp, vp, vp, vp, vp],
     "pz_shutdown": [],
     "pz_state_new": [u64, ctypes.c_int, vp],
     "pz_state_upload": [vp, vp, vp, vp],
@@ -270,6 +277,17 @@ class VoteColsBatch(ctypes.Structure):
     ]
 
 
+class RecalcBatch(ctypes.Structure):
+    """Mirror of ``pz_recalc_batch`` (include/prysm_hip.h)."""
+    _fields_ = [
+        ("nval", u64), ("balance", vp), ("start", vp), ("end", vp), ("members", vp), ("coffs", vp), ("recent", vp),
+        ("n_recent", u64), ("block_slot", u64),
+    ]
+
+
+RS_LAST_STATE_RECALC, RS_JUSTIFIED_STREAK, RS_LAST_JUSTIFIED_SLOT, RS_LAST_FINALIZED_SLOT, RS_CURRENT_DYNASTY, \
+    RS_TOTAL_DEPOSITS = range(6)  # pz_recalc_state's scalars
+RS_COUNT = 8
 SCAL_POP, SCAL_NACT, SCAL_ERR_XL, SCAL_ERR_RWD, SCAL_APPLIED, SCAL_NEXT_BAL, SCAL_MAXIDX1, SCAL_NOMATCH = range(8)
 SCAL_COUNT = 8
 KIND_ACTIVE, KIND_EXITED, KIND_QUEUED = 0, 1, 2
@@ -279,7 +297,8 @@ _RESTYPES = {"pz_last_error": ctypes.c_char_p, "pz_chain_free": None, "pz_set_se
              "pz_wire_attestations_bound": u64, "pz_wire_attestations_scratch_bytes": u64,
              "pz_unwire_attestations_scratch_bytes": u64, "pz_unwire_blocks_scratch_bytes": u64,
              "pz_vote_cache_free": None, "pz_vote_cache_scratch_bytes": u64,
-             "pz_att_pool_free": None, "pz_att_pool_scratch_bytes": u64}
+             "pz_att_pool_free": None, "pz_att_pool_scratch_bytes": u64,
+             "pz_recalc_state_free": None, "pz_state_recalc_scratch_bytes": u64}
 SERIAL_DEFAULT = 65536        # the library's default serial threshold (bytes)
 SERIAL_ON_GPU = (1 << 64) - 1  # pz_set_serial_threshold value that keeps every message on the GPU
 

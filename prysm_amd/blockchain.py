@@ -466,6 +466,40 @@ def state_recalc_device(pool, cache, state, recent_hashes, block_slot):
     return win
 
 
+def state_recalc_resident(pool, cache, state, recent_hashes, block_slot):
+    """stateRecalc (blockchain/core.go:398-497) as ONE ABI call, ``pz_dev_state_recalc``, over what
+    lives on the device: ``pool`` (a ``prysm_amd.pending.DevicePendingAttestations``), ``cache`` (a
+    ``prysm_amd.votes.DeviceVoteCache``, looked up on the device -- the map is not downloaded; None:
+    no entry) and ``state`` (a ``prysm_amd.pending.ResidentRecalcState``, advanced in place).
+    ``recent_hashes`` = RecentBlockHashes() and ``block_slot`` = the transition block's SlotNumber.
+    Computes what ``state_recalc_device`` computes and raises ``ChainPanic`` where it does; a
+    pending ShardBlockHash longer than the state's ``hash_stride`` is refused whole (PZ_ERANGE).
+    Returns the winners (one attestation row per record, 0xFFFFFFFF: none)."""
+    import torch
+
+    dev = state.balance.device
+    recent = _recent_array(recent_hashes)
+    d_recent = _to_device(recent if len(recent) else np.zeros((1, 32), np.uint8), dev)
+    b = _lib.RecalcBatch(nval=state.nval, balance=state.balance.data_ptr(), start=state.start.data_ptr(),
+                         end=state.end.data_ptr(), members=state.members.data_ptr(), coffs=state.coffs.data_ptr(),
+                         recent=d_recent.data_ptr(), n_recent=len(recent), block_slot=int(block_slot))
+    nbytes = int(lib.dll.pz_state_recalc_scratch_bytes(state.nval, int(pool.caps[0]), state.nrec))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rc = lib.dll.pz_dev_state_recalc(state._h, pool._h, cache._h if cache is not None else None, ctypes.byref(b),
+                                     scratch.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    msg = lib.dll.pz_last_error().decode() if rc != _lib.PZ_OK else ""
+    if rc == _lib.PZ_EINDEX:
+        raise ChainPanic(msg)
+    if rc != _lib.PZ_OK:
+        raise _lib.PzError(rc, msg)
+    try:
+        return state.winners()
+    except _lib.PzError as e:
+        if e.code == _lib.PZ_EINDEX:
+            raise ChainPanic(str(e)) from None
+        raise
+
+
 def serialize_blocks(blocks):
     """pb.BeaconBlock list -> (uint8 data, uint64 offsets[n+1]) of canonical encodings."""
     enc = [wire.beacon_block(b) for b in blocks]

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "attpool_dev.h"
+#include "resident.h"
 #include "runtime.h"
 #include "tile_scan.h"
 
@@ -391,6 +392,27 @@ int down(T* host, const void* dev, uint64_t count) {
 }
 
 }  // namespace
+
+int att_pool_peek(pz_att_pool* h, ApView* v, hipStream_t s) {
+  if (!h || !v) return fail(PZ_EINVAL, "attestation pool is null");
+  std::lock_guard<std::mutex> lk(h->mu);
+  const ApDst d = set_dst(h, h->live);
+  v->device = h->device;
+  v->rows_cap = h->cap[kApRows];
+  v->rows_ub = h->rows_ub;
+  v->cols = as_cols(d);
+  v->committee = d.committee;
+  v->shard32 = d.shard32;
+  v->counts = static_cast<const uint64_t*>(h->words.ptr);
+  h->last = s;
+  return PZ_OK;
+}
+
+void att_pool_note_rows(pz_att_pool* h, uint64_t rows) {
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->rows_ub = rows;
+}
+
 }  // namespace pz
 
 using namespace pz;

@@ -26,6 +26,9 @@
 //             back to empty, sets the sticky error word and marks the call void: a call lands
 //             whole or not at all.
 //   4 tally   a wave per (attestation, parent r): tally_item into the parent's slot.
+//
+// A lookup (the `if _, ok := blockVoteCache[blockHash]` of core.go:414-418) is one launch between
+// calls: a lane per query walks the table with votecache_dev.h's vc_probe, plain loads only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -33,6 +36,7 @@
 #include <mutex>
 #include <vector>
 
+#include "resident.h"
 #include "runtime.h"
 #include "votecache_dev.h"
 #include "votes_dev.h"
@@ -263,6 +267,30 @@ extern "C" __global__ void __launch_bounds__(kThreads) pz_vc_tally_kernel(VcArgs
              a.bitmaps + (uint64_t)slot * a.words, a.totals + slot, a.err);
 }
 
+// ---- lookup: a read between calls ---------------------------------------------------------------
+// A lane per query.  No launch writes the table, the keys or nslots while this one runs (the
+// caller orders it after the cache's earlier calls), so none of the intern launch's atomics.
+struct VcLookupArgs {
+  const uint32_t* table;
+  const uint8_t* keys;
+  const uint32_t* nslots;
+  const uint64_t* totals;
+  uint32_t slot_cap, cells;
+  const uint8_t* hashes;  // n x 32 B, 16-byte aligned
+  uint64_t n;
+  uint64_t* out_totals;
+  uint32_t* out_slots;  // optional
+};
+
+extern "C" __global__ void __launch_bounds__(kThreads) pz_vc_lookup_kernel(VcLookupArgs a) {
+  const uint64_t q = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (q >= a.n) return;
+  const uint32_t ns = *a.nslots < a.slot_cap ? *a.nslots : a.slot_cap;
+  const uint32_t slot = vc_probe(a.table, a.cells, a.keys, ns, vc_load_hash16(a.hashes + 32 * q));
+  a.out_totals[q] = slot == kVcNone ? 0 : a.totals[slot];
+  if (a.out_slots) a.out_slots[q] = slot;
+}
+
 // ---- host side ---------------------------------------------------------------------------------
 // What can be told without reading a column; 1: nothing to do.
 int check_args(const pz_vote_cache* h, const pz_vote_cols_batch* b) {
@@ -357,12 +385,82 @@ int report(int sticky) {
   return PZ_OK;
 }
 
+int check_lookup(const pz_vote_cache* h, const uint8_t* hashes, uint64_t n, const uint64_t* totals) {
+  if (!h) return fail(PZ_EINVAL, "vote cache is null");
+  if (n == 0) return 1;
+  if (!hashes || !totals) return fail(PZ_EINVAL, "lookup: null hashes / totals");
+  if (n >> 38) return fail(PZ_EINVAL, "more than 2^38 queries");
+  return PZ_OK;
+}
+
+int enqueue_lookup(pz_vote_cache* h, const uint8_t* d_hashes, uint64_t n, uint64_t* d_totals, uint32_t* d_slots,
+                   hipStream_t s) {
+  if (reinterpret_cast<uintptr_t>(d_hashes) & 15) return fail(PZ_EINVAL, "lookup: hashes must be 16-B aligned");
+  VcLookupArgs a;
+  a.table = static_cast<const uint32_t*>(h->table.ptr);
+  a.keys = static_cast<const uint8_t*>(h->keys.ptr);
+  a.nslots = static_cast<const uint32_t*>(h->words2.ptr);
+  a.totals = static_cast<const uint64_t*>(h->totals.ptr);
+  a.slot_cap = h->slot_cap, a.cells = h->cells;
+  a.hashes = d_hashes, a.n = n, a.out_totals = d_totals, a.out_slots = d_slots;
+  h->last = s;
+  hipLaunchKernelGGL(pz_vc_lookup_kernel, dim3((uint32_t)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PZ_OK : hip_fail(e, "pz_vc_lookup_kernel");
+}
+
 }  // namespace
+
+int vote_cache_view(pz_vote_cache* h, VcView* v, hipStream_t s) {
+  if (!h || !v) return fail(PZ_EINVAL, "vote cache is null");
+  std::lock_guard<std::mutex> lk(h->mu);
+  v->device = h->device;
+  v->nval = h->nval;
+  v->slot_cap = h->slot_cap, v->cells = h->cells;
+  v->table = static_cast<const uint32_t*>(h->table.ptr);
+  v->keys = static_cast<const uint8_t*>(h->keys.ptr);
+  v->nslots = static_cast<const uint32_t*>(h->words2.ptr);
+  v->totals = static_cast<const uint64_t*>(h->totals.ptr);
+  h->last = s;
+  return PZ_OK;
+}
+
 }  // namespace pz
 
 using namespace pz;
 
 extern "C" {
+
+int pz_dev_vote_cache_lookup(pz_vote_cache* h, const uint8_t* d_hashes, uint64_t n, uint64_t* d_totals, uint32_t* d_slots,
+                             void* stream) {
+  int rc = check_lookup(h, d_hashes, n, d_totals);
+  if (rc) return rc < 0 ? rc : PZ_OK;
+  if ((rc = use_device(h))) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  return enqueue_lookup(h, d_hashes, n, d_totals, d_slots, static_cast<hipStream_t>(stream));
+}
+
+int pz_vote_cache_lookup(pz_vote_cache* h, const uint8_t* hashes, uint64_t n, uint64_t* totals, uint32_t* slots) {
+  int rc = check_lookup(h, hashes, n, totals);
+  if (rc) return rc < 0 ? rc : PZ_OK;
+  if ((rc = use_device(h))) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  hipError_t e = hipStreamSynchronize(h->last);  // the staging stream is not the last tally's
+  if (e != hipSuccess) return hip_fail(e, "vote cache lookup");
+  DeviceCtx* c;
+  if ((rc = device_ctx(h->device, &c))) return rc;
+  std::lock_guard<std::mutex> lc(c->mu);
+  if ((rc = c->ensure_stream())) return rc;
+  Stager st{c, c->stream};
+  const uint8_t* d_hashes = st.up(hashes, n * 32);
+  uint64_t* d_totals = st.up<uint64_t>(nullptr, n);
+  uint32_t* d_slots = slots ? st.up<uint32_t>(nullptr, n) : nullptr;
+  if (st.rc) return st.rc;
+  if ((rc = enqueue_lookup(h, d_hashes, n, d_totals, d_slots, st.s))) return rc;
+  st.down(totals, static_cast<const uint64_t*>(d_totals), n);
+  if (slots) st.down(slots, static_cast<const uint32_t*>(d_slots), n);
+  return st.sync();
+}
 
 int pz_vote_cache_new(uint64_t nval, uint32_t slot_cap, int device, pz_vote_cache** out) {
   if (!out) return fail(PZ_EINVAL, "out is null");

@@ -62,6 +62,30 @@ PZ_HD Hash32 vc_load_hash(const uint8_t* p) {
   return h;
 }
 
+// The 32 bytes at a 16-byte aligned p as two 16-byte loads (a query row, keys[slot]).
+PZ_HD Hash32 vc_load_hash16(const uint8_t* p) {
+  const uint8_t* q = static_cast<const uint8_t*>(__builtin_assume_aligned(p, 16));
+  Hash32 h;
+  __builtin_memcpy(&h.w[0], q, 16);
+  __builtin_memcpy(&h.w[4], q + 16, 16);
+  return h;
+}
+
+// A read of the table between calls (no launch writes it meanwhile: plain loads): the slot of h,
+// or kVcNone.  `if _, ok := blockVoteCache[blockHash]` (core.go:414).  Probes from the home cell
+// for at most `cells` steps; an empty cell ends the probe; a cell holding a slot id below nslots
+// is compared with keys[slot] (32-byte aligned); any other value -- a claim, which cannot exist
+// between calls, or an id the cache never gave out -- is skipped and never used as an index.
+PZ_HD uint32_t vc_probe(const uint32_t* table, uint32_t cells, const uint8_t* keys, uint32_t nslots, const Hash32& h) {
+  uint32_t c = vc_home(h, cells);
+  for (uint32_t step = 0; step < cells; ++step, c = vc_next(c, cells)) {
+    const uint32_t v = table[c];
+    if (vc_is_empty(v)) return kVcNone;
+    if (v < nslots && vc_hash_eq(h, vc_load_hash16(keys + 32ull * v))) return v;
+  }
+  return kVcNone;
+}
+
 // common.BytesToHash of data[lo .. hi): the last 32 bytes of a longer range, a shorter one
 // right-aligned behind zeros.  Reads only bytes of the range.  (hi < lo counts as empty.)
 PZ_HD Hash32 vc_bytes_to_hash(const uint8_t* data, uint64_t lo, uint64_t hi) {

@@ -7,7 +7,10 @@ pending attestations (computeNewActiveState, core.go:223-237) and feed the cycle
 from the decoder's columns and the checks' outputs where they lie, pruned by slot, and read in
 place -- as the epoch kernels' attestation inputs, as the columns ``pz_dev_wire_attestations``
 encodes into the stored ActiveState's field 1, and as the crosslink winners' ShardBlockHash.
-``RecalcState`` is the CrystallizedState side of ``blockchain.state_recalc_device``.
+``RecalcState`` is the CrystallizedState side of ``blockchain.state_recalc_device``;
+``ResidentRecalcState`` (``pz_recalc_state``, prysm_amd/csrc/recalc.hip) is the same state with its
+scalars and crosslink records resident on the device, advanced by ``blockchain.state_recalc_resident``
+in one ABI call.
 """
 import numpy as np
 
@@ -260,4 +263,88 @@ class RecalcState:
         return self.balance.cpu().numpy().view(np.uint64)
 
 
-__all__ = ["DevicePendingAttestations", "RecalcState", "CAPS"]
+class ResidentRecalcState:
+    """The CrystallizedState ``blockchain.state_recalc_resident`` advances, resident on one device
+    (``pz_recalc_state``, prysm_amd/csrc/recalc.hip): ``RecalcState``'s constructor arguments plus
+    ``hash_stride`` (the bytes a crosslink record's hash may take, a multiple of 16 in [32, 256]).
+    The validators and the committee CSR are device tensors as in ``RecalcState``; the scalars and
+    the crosslink records live in the handle and come back through ``read()``.  A panic of the
+    reference (PZ_EINDEX) is sticky and raised by every read; ``strict=False`` returns what the
+    handle holds -- the state before the panicking call -- regardless."""
+
+    _SCALARS = ("last_state_recalc", "justified_streak", "last_justified_slot", "last_finalized_slot", "current_dynasty",
+                "total_deposits")
+
+    def __init__(self, balance, start_dynasty, end_dynasty, members, coffs, crosslink_records, *, last_state_recalc=0,
+                 justified_streak=0, last_justified_slot=0, last_finalized_slot=0, current_dynasty=1, total_deposits=0,
+                 device=0, hash_stride=32):
+        import torch
+
+        from prysm_amd.blockchain import _to_device
+
+        dev = torch.device("cuda", device)
+        u64 = lambda a: _to_device(np.ascontiguousarray(a, dtype=np.uint64), dev)  # noqa: E731
+        self.device, self.hash_stride = device, int(hash_stride)
+        self.balance, self.start, self.end = u64(balance), u64(start_dynasty), u64(end_dynasty)
+        members = np.ascontiguousarray(members, dtype=np.uint32)
+        self.members = _to_device(members if members.size else np.zeros(1, np.uint32), dev)
+        self.coffs = u64(coffs)
+        recs = list(crosslink_records)
+        self.nrec = len(recs)
+        scalars = np.zeros(_lib.RS_COUNT, dtype=np.uint64)
+        scalars[:6] = [int(last_state_recalc), int(justified_streak), int(last_justified_slot), int(last_finalized_slot),
+                       int(current_dynasty), int(total_deposits)]
+        dyn = np.array([r.dynasty for r in recs], dtype=np.uint64)
+        slot = np.array([r.slot for r in recs], dtype=np.uint64)
+        offs = np.zeros(self.nrec + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(r.blockhash) for r in recs], dtype=np.uint64)
+        data = np.frombuffer(b"".join(bytes(r.blockhash) for r in recs), dtype=np.uint8)
+        self._h = _lib.ctypes.c_void_p()
+        lib.call("pz_recalc_state_new", self.nrec, self.hash_stride, scalars.ctypes.data, _lib.ptr(dyn), _lib.ptr(slot),
+                 _lib.ptr(data), offs.ctypes.data, device, _lib.ctypes.byref(self._h))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            lib.dll.pz_recalc_state_free(h)
+            self._h = None
+
+    @property
+    def nval(self):
+        return int(self.balance.numel())
+
+    def balances(self):
+        return self.balance.cpu().numpy().view(np.uint64)
+
+    def read(self, strict=True):
+        """``{"scalars": uint64[8], "rec_dynasty", "rec_slot", "rec_hash" (nrec, hash_stride) uint8,
+        "rec_hash_len", "winner"}`` (``pz_recalc_state_read``; waits for the last call)."""
+        n = max(self.nrec, 1)
+        out = {"scalars": np.zeros(_lib.RS_COUNT, np.uint64), "rec_dynasty": np.zeros(n, np.uint64),
+               "rec_slot": np.zeros(n, np.uint64), "rec_hash": np.zeros((n, self.hash_stride), np.uint8),
+               "rec_hash_len": np.zeros(n, np.uint32), "winner": np.full(n, 0xFFFFFFFF, np.uint32)}
+        rc = lib.dll.pz_recalc_state_read(self._h, *[out[k].ctypes.data for k in
+                                                     ("scalars", "rec_dynasty", "rec_slot", "rec_hash", "rec_hash_len", "winner")])
+        if rc != _lib.PZ_OK and (strict or rc != _lib.PZ_EINDEX):
+            raise _lib.PzError(rc, lib.dll.pz_last_error().decode())
+        return {k: (v if k == "scalars" else v[:self.nrec]) for k, v in out.items()}
+
+    def scalar(self, index, strict=True):
+        return int(self.read(strict)["scalars"][index])
+
+    @property
+    def crosslink_records(self):
+        r = self.read(strict=False)
+        return [pb.CrosslinkRecord(int(r["rec_dynasty"][i]), r["rec_hash"][i, :int(r["rec_hash_len"][i])].tobytes(),
+                                   int(r["rec_slot"][i])) for i in range(self.nrec)]
+
+    def winners(self, strict=True):
+        """The last call's winners: one pool row (before the prune) per record, 0xFFFFFFFF: none."""
+        return self.read(strict)["winner"]
+
+
+for _i, _name in enumerate(ResidentRecalcState._SCALARS):
+    setattr(ResidentRecalcState, _name, property(lambda self, _i=_i: self.scalar(_i, strict=False)))
+
+
+__all__ = ["DevicePendingAttestations", "RecalcState", "ResidentRecalcState", "CAPS"]

@@ -169,6 +169,34 @@ class DeviceVoteCache:
         hashes, totals = self.read(strict)
         return {hashes[i].tobytes(): int(totals[i]) for i in range(len(totals))}
 
+    def lookup(self, hashes):
+        """``(totals uint64, slots uint32)`` of the given 32-byte hashes (a list of byte strings or
+        a (k, 32) uint8 array): VoteTotalDeposit, 0 when the map has no entry, and the slot id,
+        0xFFFFFFFF when absent (``pz_vote_cache_lookup``: the table is probed on the device, the
+        map is not downloaded).  Raises no sticky error."""
+        if isinstance(hashes, np.ndarray):
+            q = np.ascontiguousarray(hashes, dtype=np.uint8).reshape(-1, 32)
+        else:
+            q = np.frombuffer(b"".join(bytes(h) for h in hashes), dtype=np.uint8).reshape(-1, 32)
+        totals = np.zeros(len(q), dtype=np.uint64)
+        slots = np.zeros(len(q), dtype=np.uint32)
+        lib.call("pz_vote_cache_lookup", self._h, ptr(q), len(q), ptr(totals), ptr(slots))
+        return totals, slots
+
+    def lookup_device(self, hashes, want_slots=True):
+        """The same lookup over a device tensor ((k, 32) uint8, 16-byte aligned) on the current
+        stream, asynchronous (``pz_dev_vote_cache_lookup``): ``(totals int64, slots int32 or
+        None)`` device tensors, to be read as unsigned."""
+        import torch
+
+        n = int(hashes.numel()) // 32
+        totals = torch.empty(n, dtype=torch.int64, device=hashes.device)
+        slots = torch.empty(n, dtype=torch.int32, device=hashes.device) if want_slots else None
+        p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        lib.call("pz_dev_vote_cache_lookup", self._h, p(hashes), n, p(totals), p(slots),
+                 _lib.ctypes.c_void_p(torch.cuda.current_stream(hashes.device).cuda_stream))
+        return totals, slots
+
     def _voters(self, h, strict):
         words = np.zeros(self.words, dtype=np.uint32)
         present = _lib.ctypes.c_int(0)
