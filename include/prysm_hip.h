@@ -822,8 +822,9 @@ typedef struct pz_vote_cols_batch {   /* every member a pointer or a uint64_t */
 } pz_vote_cols_batch;
 /* Device pointers, caller's stream, asynchronous; d_scratch holds pz_vote_cache_scratch_bytes(...). */
 int pz_dev_vote_cache_tally(pz_vote_cache* cache, const pz_vote_cols_batch* b, void* d_scratch, void* stream);
-/* Host pointers (ranges start at 0), synchronous.  Errors the kernels find are sticky and
- * reported by the two calls below, not here. */
+/* Host pointers (ranges start at 0), synchronous; waits for the stream of the cache's last call
+ * first.  Only the elements the rows name are staged: n_oblique_total is a bound here.  Errors the
+ * kernels find are sticky and reported by the two calls below, not here. */
 int pz_vote_cache_tally(pz_vote_cache* cache, const pz_vote_cols_batch* b);
 /* The map's entries in slot order (the deterministic order above): *count of them; hashes[32 i]
  * and totals[i] (VoteTotalDeposit) are filled when cap >= *count.  Waits for the stream of the
@@ -891,8 +892,8 @@ uint64_t pz_att_pool_scratch_bytes(uint64_t n);
 int pz_dev_att_pool_append(pz_att_pool* pool, const pz_attestation_cols* a, uint64_t n, const int32_t* status,
                            const uint32_t* committee, const uint8_t* take /* optional */, void* d_scratch, void* stream);
 /* The same append (service.go:300, core.go:223-237) over host pointers (ranges start at 0),
- * synchronous.  Errors the kernels find are sticky and reported by pz_att_pool_counts /
- * pz_att_pool_read, not here. */
+ * synchronous; waits for the stream of the pool's last call first.  Errors the kernels find are
+ * sticky and reported by pz_att_pool_counts / pz_att_pool_read, not here. */
 int pz_att_pool_append(pz_att_pool* pool, const pz_attestation_cols* a, uint64_t n, const int32_t* status,
                        const uint32_t* committee, const uint8_t* take /* optional */);
 /* stateRecalc's filter, core.go:444-450: keeps, in order, the rows with slot > last_state_recalc.

@@ -344,6 +344,67 @@ def ptr(a):
     return a.ctypes.data if a.size else None
 
 
+def dptr(t):
+    """Device address of a torch tensor (None for None and for an empty one)."""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def stream_ptr(device):
+    """The current torch stream of ``device`` (an index or a ``torch.device``) as the ABI's ``void*``."""
+    import torch
+
+    dev = torch.device("cuda", device) if isinstance(device, int) else device
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+ATT_COLS = tuple(k for k, _ in AttestationCols._fields_)
+_ATT_DATA = ("justified_block_hash", "shard_block_hash", "attester_bitfield", "oblique_parent_hashes", "aggregate_sig")
+
+
+def att_cols(cols, keys=ATT_COLS):
+    """``AttestationCols`` over the columns of ``cols`` named by ``keys``: numpy arrays (host
+    addresses) or torch tensors (device addresses).  A missing, None or empty column is NULL, with
+    one exception: a data column with no entry still needs an address, since the entry points refuse
+    offsets without their data column, so it gets a one-entry placeholder.  The struct keeps what
+    its addresses point into alive (``_keep``)."""
+    c = AttestationCols()
+    c._keep = []
+    for k in keys:
+        v = cols.get(k)
+        if v is None:
+            continue
+        host = not hasattr(v, "data_ptr")
+        v = np.ascontiguousarray(v) if host else v
+        if k in _ATT_DATA and not (v.size if host else v.numel()):
+            v = np.zeros(1, dtype=v.dtype) if host else v.new_zeros(1)
+        if v.size if host else v.numel():
+            setattr(c, k, v.ctypes.data if host else v.data_ptr())
+            c._keep.append(v)
+    return c
+
+
+class Handle:
+    """A resident handle of the library: the ``void*`` ``_new`` fills, freed by the entry point
+    named ``_FREE`` when the object goes.  ``_STICKY``: the codes of the handle's sticky errors."""
+    _FREE = None
+    _STICKY = ()
+
+    def _new(self, name, *args):
+        self._h = ctypes.c_void_p()
+        lib.call(name, *args, ctypes.byref(self._h))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            getattr(lib.dll, self._FREE)(h)
+            self._h = None
+
+    def _rc(self, rc, strict=True, sticky_codes=None):
+        """Raises unless ``rc`` is PZ_OK, or a sticky code while ``strict`` is off."""
+        if rc != PZ_OK and (strict or rc not in (self._STICKY if sticky_codes is None else sticky_codes)):
+            raise PzError(rc, lib.dll.pz_last_error().decode())
+
+
 def as_u8(buf):
     return np.frombuffer(bytes(buf), dtype=np.uint8) if not isinstance(buf, np.ndarray) else buf
 

@@ -127,7 +127,7 @@ def _split_decode_check(payload, offsets, last_justified_slot, last_state_recalc
         blk["att_block_slot"].data_ptr(), last_justified_slot, last_state_recalc, n_recent,
         len(shard_and_committees), *[t.data_ptr() for t in table], status.data_ptr(),
         comm.data_ptr() if want_committee else None, pstart.data_ptr(), att["last_byte"].data_ptr())
-    lib.call("pz_dev_check_attestations", ctypes.byref(b), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    lib.call("pz_dev_check_attestations", ctypes.byref(b), _lib.stream_ptr(dev))
     rec = att["status"][:natt]
     status = torch.where(rec != 0, rec, status[:natt])
     block_status = wire.folded_block_status(blk["status"], blk["att_block"][:natt], rec)
@@ -179,7 +179,7 @@ def attestation_messages(cols, n, status, parents_start, recent_hashes):
     of byte strings, normalised here, or a (k, 32) uint8 array): ``pz_attestation_messages``.
     Returns ``(digests (n, 64) uint8, msg_len (n) uint32)``; a row that is not PROCESSED has a
     zero digest and length 0."""
-    keep = {k: np.ascontiguousarray(cols[k]) for k in _MSG_COLS if cols.get(k) is not None}
+    c = _lib.att_cols(cols, _MSG_COLS)
     status = np.ascontiguousarray(status, dtype=np.int32)
     pstart = np.ascontiguousarray(parents_start, dtype=np.uint64)
     recent = _recent_array(recent_hashes)
@@ -187,7 +187,7 @@ def attestation_messages(cols, n, status, parents_start, recent_hashes):
     mlen = np.zeros(n, dtype=np.uint32)
     b = _lib.AttMsgBatch(natt=n, status=_lib.ptr(status), parents_start=_lib.ptr(pstart), recent=_lib.ptr(recent),
                          n_recent=len(recent), out=_lib.ptr(out), msg_len=_lib.ptr(mlen),
-                         **{k: v.ctypes.data for k, v in keep.items()})
+                         **{k: getattr(c, k) for k in _MSG_COLS})
     lib.call("pz_attestation_messages", ctypes.byref(b))
     return out, mlen
 
@@ -203,12 +203,13 @@ def attestation_messages_device(cols, n, status, parents_start, recent, n_recent
     dev = status.device
     out = torch.empty((n, 64), dtype=torch.uint8, device=dev)
     mlen = torch.empty(n, dtype=torch.int32, device=dev)
+    c = _lib.att_cols(cols, _MSG_COLS)
     b = _lib.AttMsgBatch(natt=n, status=status.data_ptr(), parents_start=parents_start.data_ptr(),
                          recent=recent.data_ptr() if recent.numel() else None,
                          n_recent=recent.numel() // 32 if n_recent is None else n_recent,
                          out=out.data_ptr() if n else None, msg_len=mlen.data_ptr() if n else None,
-                         **{k: cols[k].data_ptr() for k in _MSG_COLS if cols.get(k) is not None})
-    lib.call("pz_dev_attestation_messages", ctypes.byref(b), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                         **{k: getattr(c, k) for k in _MSG_COLS})
+    lib.call("pz_dev_attestation_messages", ctypes.byref(b), _lib.stream_ptr(dev))
     return out, mlen
 
 
@@ -246,7 +247,7 @@ def digest_serialized_blocks(data, offsets, last_justified_slot, last_state_reca
                             want_committee=False)
     d_bytes, d_offs, blk, att, natt = d["d_bytes"], d["d_offs"], d["blk"], d["att"], d["natt"]
     rec, status, pstart, block_status = d["rec"], d["status"], d["parents_start"], d["block_status"]
-    sh = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    sh = _lib.stream_ptr(dev)
 
     block_hash = torch.empty((n, 32), dtype=torch.uint8, device=dev)
     att_hash = torch.empty((natt, 32), dtype=torch.uint8, device=dev)
@@ -445,7 +446,7 @@ def state_recalc_device(pool, cache, state, recent_hashes, block_slot):
     b.scal = red.data_ptr()
     b.vote, b.total = red[_lib.SCAL_COUNT:].data_ptr(), red[_lib.SCAL_COUNT + max(natt, 1):].data_ptr()
     b.act_mask, b.blk_cnt, b.act_list = act_mask.data_ptr(), blk_cnt.data_ptr(), act_list.data_ptr()
-    sh = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    sh = _lib.stream_ptr(dev)
     lib.call("pz_dev_epoch_count", ctypes.byref(b), sh)
     lib.call("pz_dev_epoch_finish", ctypes.byref(b), sh)
     scal = red[:_lib.SCAL_COUNT].cpu().numpy().view(np.uint64)
@@ -486,7 +487,7 @@ def state_recalc_resident(pool, cache, state, recent_hashes, block_slot):
     nbytes = int(lib.dll.pz_state_recalc_scratch_bytes(state.nval, int(pool.caps[0]), state.nrec))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     rc = lib.dll.pz_dev_state_recalc(state._h, pool._h, cache._h if cache is not None else None, ctypes.byref(b),
-                                     scratch.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                     scratch.data_ptr(), _lib.stream_ptr(dev))
     msg = lib.dll.pz_last_error().decode() if rc != _lib.PZ_OK else ""
     if rc == _lib.PZ_EINDEX:
         raise ChainPanic(msg)

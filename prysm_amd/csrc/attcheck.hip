@@ -13,10 +13,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
-#include <vector>
 
-#include "runtime.h"
+#include "att_cols.h"
+#include "resident.h"
 
 namespace pz {
 namespace {
@@ -258,7 +257,7 @@ int check_args(const pz_att_check_batch* b) {
 
 hipError_t launch_att_check(const pz_att_check_batch& b, hipStream_t s) {
   if (!b.natt) return hipSuccess;
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  auto al = aligned16;
   const bool paired = al(b.slot) && al(b.block_slot) && al(b.justified_slot) && al(b.n_oblique) && al(b.shard_id) &&
                   al(b.boffs) && (reinterpret_cast<uintptr_t>(b.status) & 7) == 0 &&
                   (!b.committee || (reinterpret_cast<uintptr_t>(b.committee) & 7) == 0) &&
@@ -307,20 +306,19 @@ int pz_check_attestations(const pz_att_check_batch* hb) {
   uint64_t ncomm = 0;  // committee ids must index coffs
   for (uint64_t e = 0; hb->narr && e < hb->arr_offs[hb->narr]; ++e)
     ncomm = std::max<uint64_t>(ncomm, (uint64_t)hb->arr_comm[e] + 1);
-  DeviceCtx* c;
-  if ((rc = acquire(&c))) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = c->ensure_stream())) return rc;
-  Stager st{c, c->stream};
+  HostForm f;  // (no handle: the current device's context)
+  if (f.rc) return f.rc;
+  Stager& st = f.st;
   pz_att_check_batch d = *hb;
   d.slot = st.up(hb->slot, n);
   d.justified_slot = st.up(hb->justified_slot, n);
   d.shard_id = st.up(hb->shard_id, n);
   d.n_oblique = st.up(hb->n_oblique, n);
   d.block_slot = st.up(hb->block_slot, n);
-  std::vector<uint64_t> bo = rebase(hb->boffs, n);
-  d.bits = st.up(hb->bits ? hb->bits + hb->boffs[0] : nullptr, bo[n]);
-  d.boffs = st.up(bo.data(), n + 1);
+  pz_attestation_cols hc{}, dc;
+  hc.attester_bitfield = hb->bits, hc.attester_bitfield_offs = hb->boffs;
+  stage_att_cols(st, hc, n, kAttBitsCols, &dc);
+  d.bits = dc.attester_bitfield, d.boffs = dc.attester_bitfield_offs;
   if (hb->narr) {
     const uint64_t ne = hb->arr_offs[hb->narr];
     d.arr_offs = st.up(hb->arr_offs, hb->narr + 1);

@@ -17,10 +17,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <vector>
-
+#include "att_cols.h"
 #include "blake2b_dev.h"
-#include "runtime.h"
+#include "resident.h"
 
 namespace pz {
 namespace {
@@ -358,8 +357,6 @@ extern "C" __global__ void __launch_bounds__(kThreads) pz_att_msg_kernel(pz_att_
 }
 
 // ---- launchers and argument checks -----------------------------------------------------------
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // Both forms; 1: nothing to do.
 int check_key_args(const pz_attestation_cols* a, uint64_t n, const uint8_t* out, uint32_t out_bytes) {
   if (out_bytes != 32 && out_bytes != 64) return fail(PZ_EINVAL, "out_bytes must be 32 or 64");
@@ -396,40 +393,15 @@ hipError_t launch_att_msgs(const pz_att_msg_batch& b, hipStream_t s) {
   return hipGetLastError();
 }
 
-// The columns both messages read, staged for the host-pointer forms (ranges rebased to 0).
-struct StagedCols {
-  const uint64_t *slot = nullptr, *shard_id = nullptr;
-  const uint8_t* sbh = nullptr;
-  const uint64_t* sbh_offs = nullptr;
-  const uint8_t* obl = nullptr;
-  const uint64_t *ooffs = nullptr, *first = nullptr;
-};
-
-int stage_cols(Stager& st, uint64_t n, const uint64_t* slot, const uint64_t* shard_id, const uint8_t* sbh,
-               const uint64_t* sbh_offs, const uint8_t* obl, const uint64_t* ooffs, const uint64_t* first,
-               StagedCols* d) {
+// The host forms' validation of the columns both messages read (kAttKeyCols), before they are staged.
+int check_key_cols(const pz_attestation_cols& a, uint64_t n) {
   int rc;
-  if (slot) d->slot = st.up(slot, n);
-  if (shard_id) d->shard_id = st.up(shard_id, n);
-  if (sbh_offs) {
-    if ((rc = check_csr(sbh_offs, n, "shard_block_hash"))) return rc;
-    std::vector<uint64_t> so = rebase(sbh_offs, n);
-    d->sbh = st.up(sbh + sbh_offs[0], so[n]);
-    d->sbh_offs = st.up(so.data(), n + 1);
-    if ((rc = st.sync())) return rc;  // (the rebased offsets leave scope)
+  if (a.shard_block_hash_offs && (rc = check_csr(a.shard_block_hash_offs, n, "shard_block_hash"))) return rc;
+  if (a.oblique_first) {
+    if ((rc = check_csr(a.oblique_first, n, "oblique_first"))) return rc;
+    if ((rc = check_csr(a.oblique_offs + a.oblique_first[0], a.oblique_first[n] - a.oblique_first[0], "oblique"))) return rc;
   }
-  if (first) {
-    if ((rc = check_csr(first, n, "oblique_first"))) return rc;
-    const uint64_t ne = first[n] - first[0];
-    const uint64_t* eo = ooffs + first[0];
-    if ((rc = check_csr(eo, ne, "oblique"))) return rc;
-    std::vector<uint64_t> fr = rebase(first, n), er = rebase(eo, ne);
-    d->obl = st.up(obl + eo[0], er[ne]);
-    d->ooffs = st.up(er.data(), ne + 1);
-    d->first = st.up(fr.data(), n + 1);
-    if ((rc = st.sync())) return rc;
-  }
-  return st.rc;
+  return PZ_OK;
 }
 
 }  // namespace
@@ -451,21 +423,14 @@ int pz_dev_attestation_keys(const pz_attestation_cols* a, uint64_t n, const int3
 int pz_attestation_keys(const pz_attestation_cols* a, uint64_t n, uint8_t* out, uint32_t out_bytes) {
   int rc = check_key_args(a, n, out, out_bytes);
   if (rc) return rc < 0 ? rc : PZ_OK;
-  DeviceCtx* c;
-  if ((rc = acquire(&c))) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = c->ensure_stream())) return rc;
-  Stager st{c, c->stream};
-  StagedCols d;
-  if ((rc = stage_cols(st, n, a->slot, a->shard_id, a->shard_block_hash, a->shard_block_hash_offs,
-                       a->oblique_parent_hashes, a->oblique_offs, a->oblique_first, &d)))
-    return rc;
+  if ((rc = check_key_cols(*a, n))) return rc;
+  HostForm f;  // (no handle: the current device's context)
+  if (f.rc) return f.rc;
+  Stager& st = f.st;
+  pz_attestation_cols dc;
+  stage_att_cols(st, *a, n, kAttKeyCols, &dc);
   uint8_t* d_out = st.up<uint8_t>(nullptr, n * out_bytes);
   if (st.rc) return st.rc;
-  pz_attestation_cols dc = {};
-  dc.slot = d.slot, dc.shard_id = d.shard_id;
-  dc.shard_block_hash = d.sbh, dc.shard_block_hash_offs = d.sbh_offs;
-  dc.oblique_parent_hashes = d.obl, dc.oblique_offs = d.ooffs, dc.oblique_first = d.first;
   st.check(launch_att_keys(dc, n, nullptr, d_out, out_bytes, st.s), "pz_att_key_kernel");
   st.down(out, d_out, n * out_bytes);
   return st.sync();
@@ -492,19 +457,19 @@ int pz_attestation_messages(const pz_att_msg_batch* hb) {
   if (any && hb->n_recent < kParents)
     return fail(PZ_EINVAL, "n_recent %llu < 64 with a PROCESSED row", (unsigned long long)hb->n_recent);
   if (any && !hb->recent) return fail(PZ_EINVAL, "recent is null");
-  DeviceCtx* c;
-  if ((rc = acquire(&c))) return rc;
-  std::lock_guard<std::mutex> lk(c->mu);
-  if ((rc = c->ensure_stream())) return rc;
-  Stager st{c, c->stream};
-  StagedCols d;
-  if ((rc = stage_cols(st, n, hb->slot, hb->shard_id, hb->shard_block_hash, hb->shard_block_hash_offs,
-                       hb->oblique_parent_hashes, hb->oblique_offs, hb->oblique_first, &d)))
-    return rc;
+  pz_attestation_cols hc{}, d;  // the batch's same-named members
+  hc.slot = hb->slot, hc.shard_id = hb->shard_id;
+  hc.shard_block_hash = hb->shard_block_hash, hc.shard_block_hash_offs = hb->shard_block_hash_offs;
+  hc.oblique_parent_hashes = hb->oblique_parent_hashes, hc.oblique_offs = hb->oblique_offs, hc.oblique_first = hb->oblique_first;
+  if ((rc = check_key_cols(hc, n))) return rc;
+  HostForm f;  // (no handle: the current device's context)
+  if (f.rc) return f.rc;
+  Stager& st = f.st;
+  stage_att_cols(st, hc, n, kAttKeyCols, &d);
   pz_att_msg_batch db = *hb;
   db.slot = d.slot, db.shard_id = d.shard_id;
-  db.shard_block_hash = d.sbh, db.shard_block_hash_offs = d.sbh_offs;
-  db.oblique_parent_hashes = d.obl, db.oblique_offs = d.ooffs, db.oblique_first = d.first;
+  db.shard_block_hash = d.shard_block_hash, db.shard_block_hash_offs = d.shard_block_hash_offs;
+  db.oblique_parent_hashes = d.oblique_parent_hashes, db.oblique_offs = d.oblique_offs, db.oblique_first = d.oblique_first;
   db.status = st.up(hb->status, n);
   db.parents_start = st.up(hb->parents_start, n);
   db.recent = st.up(hb->recent, hb->recent ? hb->n_recent * 32 : 0);

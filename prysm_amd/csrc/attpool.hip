@@ -35,32 +35,28 @@
 #include <mutex>
 #include <vector>
 
+#include "att_cols.h"
 #include "attpool_dev.h"
 #include "resident.h"
-#include "runtime.h"
 #include "tile_scan.h"
 
 namespace pz {
 namespace {
 
-constexpr int kSetBufs = 16;  // pz_attestation_cols' fourteen columns, committee, shard32
+constexpr int kSetBufs = kAttNCols + 2;  // pz_attestation_cols' columns (att_cols.h's order), committee, shard32
 
 }  // namespace
 }  // namespace pz
 
-struct pz_att_pool {
-  int device = 0;
+struct pz_att_pool : pz::Resident {  // (last: counts / read wait for it)
   uint64_t cap[pz::kApCols] = {};
-  std::mutex mu;
-  hipStream_t last = nullptr;  // the stream of the last call: counts / read wait for it
   uint64_t rows_ub = 0;        // an upper bound of the rows held (a prune's grid; exact after counts)
   int live = 0;                // which buffer set holds the rows
   pz::DevBuf set[2][pz::kSetBufs];
   pz::DevBuf words;    // counts[7], then the sticky error word
   pz::DevBuf scratch;  // a prune's scratch (sized for cap[0] rows)
   ~pz_att_pool() {
-    (void)hipSetDevice(device);
-    (void)hipStreamSynchronize(last);
+    drain();
     for (auto& s : set)
       for (pz::DevBuf& b : s) b.release();
     words.release();
@@ -237,53 +233,30 @@ extern "C" __global__ void __launch_bounds__(kTile) pz_att_pool_write_kernel(ApA
 }
 
 // ---- host side ---------------------------------------------------------------------------------
-uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
-uint64_t pad256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
 uint64_t scratch_bytes(uint64_t n) { return pad256((kApCols * tiles_of(n) + kApCols + sizeof(ApCall) / 8) * 8); }
 
-// Entries of buffer k of a set, and the width of one.
-uint64_t buf_entries(const uint64_t cap[kApCols], int k) {
-  switch (k) {
-    case 3: return cap[kApJbh] + 16;        // bytes columns: the digest kernels' 4 readable bytes and
-    case 5: return cap[kApSbh] + 16;        // the 16-byte pieces' room
-    case 7: return cap[kApBits] + 16;
-    case 9: return cap[kApElemBytes] + 16;
-    case 10: return cap[kApElems] + 1;
-    case 12: return cap[kApSigs] + 1;
-    case 4: case 6: case 8: case 11: case 13: return cap[kApRows] + 1;
-    default: return cap[kApRows];  // the scalars, committee, shard32
-  }
+// Bytes of buffer k of a set: a column at its capacity (cap[1..] are att_cols.h's totals), a bytes
+// column with the digest kernels' 4 readable bytes and the 16-byte pieces' room, the sig values
+// with one entry's; committee, shard32.
+uint64_t buf_bytes(const uint64_t cap[kApCols], int k) {
+  if (k >= kAttNCols) return cap[kApRows] * 4;
+  const AttCol& c = kAttTable[k];
+  const uint64_t room = c.total < 0 || c.plus ? 0 : c.width == 1 ? 16 : 1;
+  return (att_col_len(c, cap[kApRows], cap + 1) + room) * c.width;
 }
-uint64_t buf_width(int k) { return (k == 3 || k == 5 || k == 7 || k == 9) ? 1 : k >= 14 ? 4 : 8; }
 
 ApDst set_dst(pz_att_pool* h, int s) {
   ApDst d{};
   pz::DevBuf* b = h->set[s];
-  d.c.slot = (uint64_t*)b[0].ptr, d.c.shard_id = (uint64_t*)b[1].ptr, d.c.justified_slot = (uint64_t*)b[2].ptr;
-  d.c.justified_block_hash = (uint8_t*)b[3].ptr, d.c.justified_block_hash_offs = (uint64_t*)b[4].ptr;
-  d.c.shard_block_hash = (uint8_t*)b[5].ptr, d.c.shard_block_hash_offs = (uint64_t*)b[6].ptr;
-  d.c.attester_bitfield = (uint8_t*)b[7].ptr, d.c.attester_bitfield_offs = (uint64_t*)b[8].ptr;
-  d.c.oblique_parent_hashes = (uint8_t*)b[9].ptr, d.c.oblique_offs = (uint64_t*)b[10].ptr;
-  d.c.oblique_first = (uint64_t*)b[11].ptr;
-  d.c.aggregate_sig = (uint64_t*)b[12].ptr, d.c.aggregate_sig_first = (uint64_t*)b[13].ptr;
-  d.committee = (uint32_t*)b[14].ptr, d.shard32 = (uint32_t*)b[15].ptr;
+  for (int k = 0; k < kAttNCols; ++k) att_set_out(&d.c, k, b[k].ptr);
+  d.committee = (uint32_t*)b[kAttNCols].ptr, d.shard32 = (uint32_t*)b[kAttNCols + 1].ptr;
   return d;
 }
 
 pz_attestation_cols as_cols(const ApDst& d) {
   pz_attestation_cols c{};
-  c.slot = d.c.slot, c.shard_id = d.c.shard_id, c.justified_slot = d.c.justified_slot;
-  c.justified_block_hash = d.c.justified_block_hash, c.justified_block_hash_offs = d.c.justified_block_hash_offs;
-  c.shard_block_hash = d.c.shard_block_hash, c.shard_block_hash_offs = d.c.shard_block_hash_offs;
-  c.attester_bitfield = d.c.attester_bitfield, c.attester_bitfield_offs = d.c.attester_bitfield_offs;
-  c.oblique_parent_hashes = d.c.oblique_parent_hashes, c.oblique_offs = d.c.oblique_offs, c.oblique_first = d.c.oblique_first;
-  c.aggregate_sig = d.c.aggregate_sig, c.aggregate_sig_first = d.c.aggregate_sig_first;
+  for (int k = 0; k < kAttNCols; ++k) att_set_in(&c, k, att_out(d.c, k));
   return c;
-}
-
-int use_device(pz_att_pool* h) {
-  hipError_t e = hipSetDevice(h->device);
-  return e == hipSuccess ? PZ_OK : hip_fail(e, "hipSetDevice");
 }
 
 // What can be told about an append without reading a column; 1: nothing to do.
@@ -303,7 +276,7 @@ int check_append(const pz_att_pool* h, const pz_attestation_cols* a, uint64_t n,
 
 // The four launches on s.  scratch: tiles, totals, the call record.  ev (the A/B library's timed
 // entry; null in the product): five events, one before the first launch and one after each.
-int enqueue(pz_att_pool* h, ApArgs a, void* d_scratch, hipStream_t s, hipEvent_t* ev = nullptr) {
+int enqueue(pz_att_pool* h, ApArgs a, void* d_scratch, hipStream_t s, Events* ev = nullptr) {
   a.ntiles = tiles_of(a.n);
   std::memcpy(a.cap, h->cap, sizeof a.cap);
   a.counts = static_cast<uint64_t*>(h->words.ptr);
@@ -313,22 +286,19 @@ int enqueue(pz_att_pool* h, ApArgs a, void* d_scratch, hipStream_t s, hipEvent_t
   a.long_bytes = g_long_bytes;
   h->last = s;
   hipError_t e;
-  auto stamp = [&](int k) {
-    if (ev) (void)hipEventRecord(ev[k], s);
-  };
-  stamp(0);
+  stamp(ev, 0, s);
   hipLaunchKernelGGL(pz_att_pool_size_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_att_pool_size_kernel");
-  stamp(1);
+  stamp(ev, 1, s);
   if ((e = launch_tile_scan(a.tiles, a.ntiles, (uint32_t)kApCols, a.totals, s)) != hipSuccess)
     return hip_fail(e, "pz_unwire_scan_kernel");
-  stamp(2);
+  stamp(ev, 2, s);
   hipLaunchKernelGGL(pz_att_pool_commit_kernel, dim3(1), dim3(64), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_att_pool_commit_kernel");
-  stamp(3);
+  stamp(ev, 3, s);
   hipLaunchKernelGGL(pz_att_pool_write_kernel, dim3((uint32_t)a.ntiles), dim3(kTile), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_att_pool_write_kernel");
-  stamp(4);
+  stamp(ev, 4, s);
   return PZ_OK;
 }
 
@@ -361,10 +331,9 @@ ApArgs prune_args(pz_att_pool* h, uint64_t last_state_recalc) {
 
 // Waits for the last call and reads the counts and the sticky error word; the code to report.
 int settle(pz_att_pool* h, uint64_t counts[kApCols], int* sticky) {
-  hipError_t e = hipStreamSynchronize(h->last);
   uint64_t w[kApCols + 1] = {};
-  if (e == hipSuccess) e = hipMemcpy(w, h->words.ptr, sizeof w, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return hip_fail(e, "attestation pool read");
+  int rc = h->settle(w, h->words, sizeof w, "attestation pool read");
+  if (rc) return rc;
   std::memcpy(counts, w, kApCols * 8);
   h->rows_ub = w[kApRows];
   *sticky = (w[kApCols] & kApErrInverted) ? PZ_EINVAL : (w[kApCols] & kApErrCapacity) ? PZ_ERANGE : PZ_OK;
@@ -375,20 +344,6 @@ int report(int sticky) {
   if (sticky == PZ_EINVAL) return fail(PZ_EINVAL, "an appended row had an inverted range; it landed empty");
   if (sticky == PZ_ERANGE) return fail(PZ_ERANGE, "an append needed more than the pool holds; it was dropped whole");
   return PZ_OK;
-}
-
-// The largest entry of offs[0 .. n]: what a host column holds when its ranges start at 0.
-uint64_t span_end(const uint64_t* offs, uint64_t n) {
-  uint64_t m = 0;
-  for (uint64_t i = 0; offs && i <= n; ++i) m = std::max(m, offs[i]);
-  return m;
-}
-
-template <typename T>
-int down(T* host, const void* dev, uint64_t count) {
-  if (!host || !count) return PZ_OK;
-  hipError_t e = hipMemcpy(host, dev, count * sizeof(T), hipMemcpyDeviceToHost);
-  return e == hipSuccess ? PZ_OK : hip_fail(e, "attestation pool read");
 }
 
 }  // namespace
@@ -426,24 +381,17 @@ int pz_att_pool_new(const uint64_t caps[7], int device, pz_att_pool** out) {
   if (caps[kApRows] == 0) return fail(PZ_EINVAL, "an attestation pool of zero rows");
   for (int c = 0; c < kApCols; ++c)
     if (caps[c] >> 40) return fail(PZ_EINVAL, "capacity %d is %llu: 2^40 or more", c, (unsigned long long)caps[c]);
-  DeviceCtx* dc;
-  int rc = device_ctx(device, &dc);
+  int rc = Resident::open(device);
   if (rc) return rc;
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  hipError_t e;
   auto* h = new pz_att_pool();
   h->device = device;
   std::memcpy(h->cap, caps, sizeof h->cap);
-  for (int s = 0; s < 2 && !rc; ++s)
-    for (int k = 0; k < kSetBufs && !rc; ++k) {
-      const size_t bytes = (size_t)(buf_entries(caps, k) * buf_width(k));
-      if ((rc = h->set[s][k].reserve(bytes))) break;
-      if ((e = hipMemset(h->set[s][k].ptr, 0, bytes)) != hipSuccess) rc = hip_fail(e, "attestation pool init");
-    }
-  if (!rc) rc = h->words.reserve((kApCols + 1) * 8);
+  const char* what = "attestation pool init";
+  for (int k = 0; k < 2 * kSetBufs && !rc; ++k) rc = h->set[k / kSetBufs][k % kSetBufs].fill((size_t)buf_bytes(caps, k % kSetBufs), 0, what);
+  if (!rc) rc = h->words.fill((kApCols + 1) * 8, 0, what);
   if (!rc) rc = h->scratch.reserve(scratch_bytes(caps[kApRows]));
-  if (!rc && (e = hipMemset(h->words.ptr, 0, (kApCols + 1) * 8)) != hipSuccess) rc = hip_fail(e, "attestation pool init");
-  if (!rc && (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "attestation pool init");
+  if (!rc && (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, what);
   if (rc) {
     delete h;
     return rc;
@@ -460,9 +408,8 @@ int pz_dev_att_pool_append(pz_att_pool* h, const pz_attestation_cols* a, uint64_
                            const uint32_t* committee, const uint8_t* take, void* d_scratch, void* stream) {
   int rc = check_append(h, a, n, status, committee);
   if (rc) return rc < 0 ? rc : PZ_OK;
-  if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15))
-    return fail(PZ_EINVAL, "d_scratch must be a 16-B aligned device pointer");
-  if ((rc = use_device(h))) return rc;
+  if (!d_scratch || !aligned16(d_scratch)) return fail(PZ_EINVAL, "d_scratch must be a 16-B aligned device pointer");
+  if ((rc = h->use())) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   if ((rc = enqueue(h, append_args(h, *a, n, status, committee, take), d_scratch, static_cast<hipStream_t>(stream)))) return rc;
   h->rows_ub = std::min(h->cap[kApRows], h->rows_ub + n);
@@ -473,42 +420,11 @@ int pz_att_pool_append(pz_att_pool* h, const pz_attestation_cols* ha, uint64_t n
                        const uint32_t* committee, const uint8_t* take) {
   int rc = check_append(h, ha, n, status, committee);
   if (rc) return rc < 0 ? rc : PZ_OK;
-  if ((rc = use_device(h))) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceCtx* c;
-  if ((rc = device_ctx(h->device, &c))) return rc;
-  std::lock_guard<std::mutex> lc(c->mu);
-  Stager st{c, c->stream};
-  pz_attestation_cols d = *ha;
-  if (ha->slot) d.slot = st.up(ha->slot, n);
-  if (ha->shard_id) d.shard_id = st.up(ha->shard_id, n);
-  if (ha->justified_slot) d.justified_slot = st.up(ha->justified_slot, n);
-  if (ha->justified_block_hash_offs) {
-    d.justified_block_hash = st.up(ha->justified_block_hash, span_end(ha->justified_block_hash_offs, n));
-    d.justified_block_hash_offs = st.up(ha->justified_block_hash_offs, n + 1);
-  }
-  if (ha->shard_block_hash_offs) {
-    d.shard_block_hash = st.up(ha->shard_block_hash, span_end(ha->shard_block_hash_offs, n));
-    d.shard_block_hash_offs = st.up(ha->shard_block_hash_offs, n + 1);
-  }
-  if (ha->attester_bitfield_offs) {
-    d.attester_bitfield = st.up(ha->attester_bitfield, span_end(ha->attester_bitfield_offs, n));
-    d.attester_bitfield_offs = st.up(ha->attester_bitfield_offs, n + 1);
-  }
-  if (ha->oblique_first) {
-    const uint64_t ne = span_end(ha->oblique_first, n);
-    d.oblique_parent_hashes = st.up(ha->oblique_parent_hashes, span_end(ha->oblique_offs, ne));
-    d.oblique_offs = st.up(ha->oblique_offs, ne + 1);
-    d.oblique_first = st.up(ha->oblique_first, n + 1);
-  } else {
-    d.oblique_parent_hashes = nullptr, d.oblique_offs = nullptr;
-  }
-  if (ha->aggregate_sig_first) {
-    d.aggregate_sig = st.up(ha->aggregate_sig, span_end(ha->aggregate_sig_first, n));
-    d.aggregate_sig_first = st.up(ha->aggregate_sig_first, n + 1);
-  } else {
-    d.aggregate_sig = nullptr;
-  }
+  HostForm f(h, "attestation pool append");
+  if (f.rc) return f.rc;
+  Stager& st = f.st;
+  pz_attestation_cols d;
+  stage_att_cols(st, *ha, n, kAttAllCols, &d);
   const int32_t* d_status = st.up(status, n);
   const uint32_t* d_comm = st.up(committee, n);
   const uint8_t* d_take = take ? st.up(take, n) : nullptr;
@@ -521,7 +437,7 @@ int pz_att_pool_append(pz_att_pool* h, const pz_attestation_cols* ha, uint64_t n
 
 int pz_dev_att_pool_prune(pz_att_pool* h, uint64_t last_state_recalc, void* stream) {
   if (!h) return fail(PZ_EINVAL, "attestation pool is null");
-  int rc = use_device(h);
+  int rc = h->use();
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   if (h->rows_ub == 0) return PZ_OK;  // nothing was ever appended since the last exact count of 0
@@ -532,7 +448,7 @@ int pz_dev_att_pool_prune(pz_att_pool* h, uint64_t last_state_recalc, void* stre
 
 int pz_att_pool_counts(pz_att_pool* h, uint64_t counts[7]) {
   if (!h || !counts) return fail(PZ_EINVAL, "attestation pool / counts is null");
-  int rc = use_device(h);
+  int rc = h->use();
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   int sticky;
@@ -552,41 +468,29 @@ int pz_att_pool_view(pz_att_pool* h, pz_attestation_cols* cols, const uint32_t**
 
 int pz_att_pool_read(pz_att_pool* h, const pz_attestation_cols_out* out, uint32_t* committee, const uint64_t caps[6]) {
   if (!h || !out || !caps) return fail(PZ_EINVAL, "attestation pool / out / caps is null");
-  int rc = use_device(h);
+  int rc = h->use();
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   uint64_t n[kApCols];
   int sticky;
   if ((rc = settle(h, n, &sticky))) return rc;
-  static const char* const kWhat[6] = {"justified_block_hash", "shard_block_hash", "attester_bitfield",
-                                       "oblique elements",     "oblique bytes",    "aggregate_sig"};
-  for (int c = 0; c < 6; ++c)
+  for (int c = 0; c < kAttTotals; ++c)
     if (n[c + 1] > caps[c])
-      return fail(PZ_ERANGE, "%s holds %llu, capacity %llu", kWhat[c], (unsigned long long)n[c + 1],
+      return fail(PZ_ERANGE, "%s holds %llu, capacity %llu", att_total_name(c), (unsigned long long)n[c + 1],
                   (unsigned long long)caps[c]);
   const ApDst d = set_dst(h, h->live);
-  const uint64_t r = n[kApRows];
-  if ((rc = down(out->slot, d.c.slot, r)) || (rc = down(out->shard_id, d.c.shard_id, r)) ||
-      (rc = down(out->justified_slot, d.c.justified_slot, r)) ||
-      (rc = down(out->justified_block_hash, d.c.justified_block_hash, n[kApJbh])) ||
-      (rc = down(out->justified_block_hash_offs, d.c.justified_block_hash_offs, r + 1)) ||
-      (rc = down(out->shard_block_hash, d.c.shard_block_hash, n[kApSbh])) ||
-      (rc = down(out->shard_block_hash_offs, d.c.shard_block_hash_offs, r + 1)) ||
-      (rc = down(out->attester_bitfield, d.c.attester_bitfield, n[kApBits])) ||
-      (rc = down(out->attester_bitfield_offs, d.c.attester_bitfield_offs, r + 1)) ||
-      (rc = down(out->oblique_parent_hashes, d.c.oblique_parent_hashes, n[kApElemBytes])) ||
-      (rc = down(out->oblique_offs, d.c.oblique_offs, n[kApElems] + 1)) ||
-      (rc = down(out->oblique_first, d.c.oblique_first, r + 1)) ||
-      (rc = down(out->aggregate_sig, d.c.aggregate_sig, n[kApSigs])) ||
-      (rc = down(out->aggregate_sig_first, d.c.aggregate_sig_first, r + 1)) || (rc = down(committee, d.committee, r)))
-    return rc;
+  for (int k = 0; k < kAttNCols; ++k) {
+    const uint64_t bytes = att_col_len(kAttTable[k], n[kApRows], n + 1) * kAttTable[k].width;
+    if ((rc = down(static_cast<uint8_t*>(att_out(*out, k)), att_out(d.c, k), bytes, "attestation pool read"))) return rc;
+  }
+  if ((rc = down(committee, d.committee, n[kApRows], "attestation pool read"))) return rc;
   return report(sticky);
 }
 
 int pz_att_pool_shard_block_hashes(pz_att_pool* h, const uint32_t* rows, uint64_t nrows, uint8_t* out, uint64_t cap,
                                    uint64_t* offs) {
   if (!h || !offs || (nrows && !rows)) return fail(PZ_EINVAL, "attestation pool / rows / offs is null");
-  int rc = use_device(h);
+  int rc = h->use();
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   uint64_t n[kApCols];
@@ -595,7 +499,8 @@ int pz_att_pool_shard_block_hashes(pz_att_pool* h, const uint32_t* rows, uint64_
   const ApDst d = set_dst(h, h->live);
   std::vector<uint64_t> so(n[kApRows] + 1);
   std::vector<uint8_t> sb(n[kApSbh]);
-  if ((rc = down(so.data(), d.c.shard_block_hash_offs, so.size())) || (rc = down(sb.data(), d.c.shard_block_hash, sb.size())))
+  if ((rc = down(so.data(), d.c.shard_block_hash_offs, so.size(), "attestation pool read")) ||
+      (rc = down(sb.data(), d.c.shard_block_hash, sb.size(), "attestation pool read")))
     return rc;
   offs[0] = 0;
   for (uint64_t k = 0; k < nrows; ++k) {
@@ -626,27 +531,22 @@ int pz_debug_att_pool_timed(pz_att_pool* h, const pz_attestation_cols* a, uint64
                             const uint32_t* committee, const uint8_t* take, uint64_t last_state_recalc, void* d_scratch,
                             void* stream, float ms[4]) {
   if (!h || !ms) return fail(PZ_EINVAL, "null pointer");
-  int rc = use_device(h);
+  int rc = h->use();
   if (rc) return rc;
   if (a && ((rc = check_append(h, a, n, status, committee)) || !d_scratch)) return rc < 0 ? rc : fail(PZ_EINVAL, "nothing to time");
   std::lock_guard<std::mutex> lk(h->mu);
   if (!a && h->rows_ub == 0) return fail(PZ_EINVAL, "nothing to time");
-  hipEvent_t ev[5];
-  for (auto& x : ev)
-    if (hipEventCreate(&x) != hipSuccess) return fail(PZ_EDEVICE, "hipEventCreate");
+  Events ev;
+  if ((rc = ev.create(5))) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (a) {
-    rc = enqueue(h, append_args(h, *a, n, status, committee, take), d_scratch, s, ev);
+    rc = enqueue(h, append_args(h, *a, n, status, committee, take), d_scratch, s, &ev);
     if (!rc) h->rows_ub = std::min(h->cap[kApRows], h->rows_ub + n);
   } else {
-    rc = enqueue(h, prune_args(h, last_state_recalc), h->scratch.ptr, s, ev);
+    rc = enqueue(h, prune_args(h, last_state_recalc), h->scratch.ptr, s, &ev);
     if (!rc) h->live ^= 1;
   }
-  hipError_t e = hipStreamSynchronize(s);
-  for (int k = 0; k < 4 && !rc && e == hipSuccess; ++k) e = hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
-  for (auto& x : ev) (void)hipEventDestroy(x);
-  if (rc) return rc;
-  return e == hipSuccess ? PZ_OK : hip_fail(e, "timed attestation pool call");
+  return ev.elapsed(rc, ms, nullptr, 4, s, "timed attestation pool call");
 }
 #endif
 

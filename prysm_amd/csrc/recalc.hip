@@ -36,18 +36,13 @@
 
 #include "recalc_dev.h"
 #include "resident.h"
-#include "runtime.h"
 
-struct pz_recalc_state {
-  int device = 0;
+struct pz_recalc_state : pz::Resident {  // (last: read waits for it)
   uint32_t nrec = 0, stride = 0;
-  std::mutex mu;
-  hipStream_t last = nullptr;  // the stream of the last call: read waits for it
   pz::DevBuf words;            // scalars[PZ_RS_COUNT], then the sticky error word
   pz::DevBuf rec_dynasty, rec_slot, rec_hash, rec_hash_len, winner;  // max(nrec, 1) entries each
   ~pz_recalc_state() {
-    (void)hipSetDevice(device);
-    (void)hipStreamSynchronize(last);
+    drain();
     for (pz::DevBuf* b : {&words, &rec_dynasty, &rec_slot, &rec_hash, &rec_hash_len, &winner}) b->release();
   }
 };
@@ -64,8 +59,6 @@ enum { kJStreak = 0, kJJustified = 1, kJFinalized = 2, kJDynasty = 3, kJLsr = 4,
 struct RsLayout {
   uint64_t fit, just, scal, vote, total, act_mask, act_list, blk_cnt, winner, end;  // byte offsets
 };
-
-constexpr uint64_t r16(uint64_t x) { return (x + 15) & ~15ull; }
 
 RsLayout layout(uint64_t nval, uint64_t rows_cap, uint32_t nrec) {
   RsLayout l;
@@ -200,32 +193,10 @@ extern "C" __global__ void __launch_bounds__(kRsThreads) pz_rs_commit_kernel(RsA
 }
 
 // ---- host side ---------------------------------------------------------------------------------
-int use_device(pz_recalc_state* h) {
-  hipError_t e = hipSetDevice(h->device);
-  return e == hipSuccess ? PZ_OK : hip_fail(e, "hipSetDevice");
-}
-
-template <typename T>
-int put(pz::DevBuf& b, const T* host, uint64_t count, uint64_t entries) {
-  const size_t bytes = (size_t)(std::max<uint64_t>(entries, 1) * sizeof(T));
-  int rc = b.reserve(bytes);
-  if (rc) return rc;
-  hipError_t e = hipMemset(b.ptr, 0, bytes);
-  if (e == hipSuccess && host && count) e = hipMemcpy(b.ptr, host, (size_t)(count * sizeof(T)), hipMemcpyHostToDevice);
-  return e == hipSuccess ? PZ_OK : hip_fail(e, "recalc state init");
-}
-
-template <typename T>
-int down(T* host, const void* dev, uint64_t count) {
-  if (!host || !count) return PZ_OK;
-  hipError_t e = hipMemcpy(host, dev, (size_t)(count * sizeof(T)), hipMemcpyDeviceToHost);
-  return e == hipSuccess ? PZ_OK : hip_fail(e, "recalc state read");
-}
-
 // The whole call on s.  ev (the A/B library's timed entry; null in the product): eight events,
 // around the fit, justify, count, finish, commit and prune steps (ev[1] .. ev[2] is the host's wait).
 int enqueue(pz_recalc_state* h, pz_att_pool* pool, pz_vote_cache* cache, const pz_recalc_batch& b, void* d_scratch,
-            hipStream_t s, hipEvent_t* ev = nullptr) {
+            hipStream_t s, Events* ev = nullptr) {
   ApView pv;
   VcView cv;
   std::memset(&cv, 0, sizeof cv);
@@ -263,21 +234,18 @@ int enqueue(pz_recalc_state* h, pz_att_pool* pool, pz_vote_cache* cache, const p
   a.scal = reinterpret_cast<uint64_t*>(p + l.scal);
   a.winner = reinterpret_cast<uint32_t*>(p + l.winner);
 
-  auto stamp = [&](int k) {
-    if (ev) (void)hipEventRecord(ev[k], s);
-  };
   hipError_t e = hipMemsetAsync(p, 0, l.winner, s);
   if (e == hipSuccess) e = hipMemsetAsync(p + l.winner, 0xFF, l.end - l.winner, s);
   if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
   h->last = s;
 
   // 1: fit, and the call's one wait
-  stamp(0);
+  stamp(ev, 0, s);
   const uint64_t rows_ub = std::min(pv.rows_ub, pv.rows_cap);
   hipLaunchKernelGGL(pz_rs_fit_kernel, dim3((uint32_t)std::max<uint64_t>((rows_ub + kRsThreads - 1) / kRsThreads, 1)),
                      dim3(kRsThreads), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_rs_fit_kernel");
-  stamp(1);
+  stamp(ev, 1, s);
   uint64_t fit[kFitWords];
   if ((e = hipMemcpyAsync(fit, a.fit, sizeof fit, hipMemcpyDeviceToHost, s)) != hipSuccess ||
       (e = hipStreamSynchronize(s)) != hipSuccess)
@@ -289,10 +257,10 @@ int enqueue(pz_recalc_state* h, pz_att_pool* pool, pz_vote_cache* cache, const p
     return fail(PZ_ERANGE, "a pending ShardBlockHash is longer than the records' stride of %u bytes; nothing changed", h->stride);
 
   // 2: justify
-  stamp(2);
+  stamp(ev, 2, s);
   hipLaunchKernelGGL(pz_rs_justify_kernel, dim3(1), dim3(64), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_rs_justify_kernel");
-  stamp(3);
+  stamp(ev, 3, s);
 
   // 3: the epoch, one instance over the pool's view
   pz_epoch_batch eb;
@@ -319,19 +287,19 @@ int enqueue(pz_recalc_state* h, pz_att_pool* pool, pz_vote_cache* cache, const p
   eb.blk_cnt = reinterpret_cast<uint32_t*>(p + l.blk_cnt);
   eb.act_list = reinterpret_cast<uint32_t*>(p + l.act_list);
   if ((rc = pz_dev_epoch_count(&eb, s))) return rc;
-  stamp(4);
+  stamp(ev, 4, s);
   if ((rc = pz_dev_epoch_finish(&eb, s))) return rc;
-  stamp(5);
+  stamp(ev, 5, s);
 
   // 4: commit
   hipLaunchKernelGGL(pz_rs_commit_kernel, dim3(std::max<uint32_t>((h->nrec + kRsThreads - 1) / kRsThreads, 1)),
                      dim3(kRsThreads), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_rs_commit_kernel");
-  stamp(6);
+  stamp(ev, 6, s);
 
   // 5: prune, by the lastStateRecalc the wait brought
   if ((rc = pz_dev_att_pool_prune(pool, fit[kFitLsr], s))) return rc;
-  stamp(7);
+  stamp(ev, 7, s);
   return PZ_OK;
 }
 
@@ -346,7 +314,7 @@ int check_call(const pz_recalc_state* h, const pz_att_pool* pool, const pz_recal
   if (!h || !pool || !b || !d_scratch) return fail(PZ_EINVAL, "recalc: null state / pool / batch / scratch");
   if (!b->balance || !b->start || !b->end || !b->members || !b->coffs || !b->recent)
     return fail(PZ_EINVAL, "recalc batch: null balance / start / end / members / coffs / recent");
-  if ((reinterpret_cast<uintptr_t>(b->recent) & 15) || (reinterpret_cast<uintptr_t>(d_scratch) & 15))
+  if (!aligned16(b->recent) || !aligned16(d_scratch))
     return fail(PZ_EINVAL, "recalc: recent and d_scratch must be 16-B aligned device pointers");
   if (b->n_recent < PZ_CYCLE_LENGTH)
     return fail(PZ_EINDEX, "stateRecalc: RecentBlockHashes()[i], index out of range with %llu hashes (core.go:413)",
@@ -377,29 +345,25 @@ int pz_recalc_state_new(uint32_t nrec, uint32_t hash_stride, const uint64_t scal
     if (hi > lo) std::memcpy(hashes.data() + (size_t)r * hash_stride, rec_hash + lo, hi - lo);
     lens[r] = (uint32_t)(hi - lo);
   }
-  DeviceCtx* dc;
-  int rc = device_ctx(device, &dc);
+  int rc = Resident::open(device);
   if (rc) return rc;
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
   auto* h = new pz_recalc_state();
   h->device = device;
   h->nrec = nrec;
   h->stride = hash_stride;
   uint64_t words[PZ_RS_COUNT + 1] = {};
   std::memcpy(words, scalars, PZ_RS_COUNT * 8);
-  if ((rc = put(h->words, words, PZ_RS_COUNT + 1, PZ_RS_COUNT + 1)) || (rc = put(h->rec_dynasty, rec_dynasty, nrec, nrec)) ||
-      (rc = put(h->rec_slot, rec_slot, nrec, nrec)) || (rc = put(h->rec_hash, hashes.data(), hashes.size(), hashes.size())) ||
-      (rc = put(h->rec_hash_len, lens.data(), lens.size(), lens.size())) ||
-      (rc = put<uint32_t>(h->winner, nullptr, 0, nrec))) {
+  const char* what = "recalc state init";
+  const size_t n1 = std::max<uint32_t>(nrec, 1);
+  hipError_t e;
+  if ((rc = h->words.fill(sizeof words, 0, what, words, sizeof words)) ||
+      (rc = h->rec_dynasty.fill(n1 * 8, 0, what, rec_dynasty, nrec * 8ull)) ||
+      (rc = h->rec_slot.fill(n1 * 8, 0, what, rec_slot, nrec * 8ull)) ||
+      (rc = h->rec_hash.fill(hashes.size(), 0, what, hashes.data(), hashes.size())) ||
+      (rc = h->rec_hash_len.fill(n1 * 4, 0, what, lens.data(), n1 * 4)) || (rc = h->winner.fill(n1 * 4, 0xFF, what)) ||
+      ((e = hipDeviceSynchronize()) != hipSuccess && (rc = hip_fail(e, what)))) {
     delete h;
     return rc;
-  }
-  e = hipMemset(h->winner.ptr, 0xFF, (size_t)std::max<uint32_t>(nrec, 1) * 4);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    delete h;
-    return hip_fail(e, "recalc state init");
   }
   *out = h;
   return PZ_OK;
@@ -410,18 +374,17 @@ void pz_recalc_state_free(pz_recalc_state* h) { delete h; }
 int pz_recalc_state_read(pz_recalc_state* h, uint64_t scalars[PZ_RS_COUNT], uint64_t* rec_dynasty, uint64_t* rec_slot,
                          uint8_t* rec_hash, uint32_t* rec_hash_len, uint32_t* winner) {
   if (!h) return fail(PZ_EINVAL, "recalc state is null");
-  int rc = use_device(h);
+  int rc = h->use();
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
-  hipError_t e = hipStreamSynchronize(h->last);
   uint64_t w[PZ_RS_COUNT + 1] = {};
-  if (e == hipSuccess) e = hipMemcpy(w, h->words.ptr, sizeof w, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return hip_fail(e, "recalc state read");
+  if ((rc = h->settle(w, h->words, sizeof w, "recalc state read"))) return rc;
   if (scalars) std::memcpy(scalars, w, PZ_RS_COUNT * 8);
   const uint64_t n = h->nrec;
-  if ((rc = down(rec_dynasty, h->rec_dynasty.ptr, n)) || (rc = down(rec_slot, h->rec_slot.ptr, n)) ||
-      (rc = down(rec_hash, h->rec_hash.ptr, n * h->stride)) || (rc = down(rec_hash_len, h->rec_hash_len.ptr, n)) ||
-      (rc = down(winner, h->winner.ptr, n)))
+  const char* what = "recalc state read";
+  if ((rc = down(rec_dynasty, h->rec_dynasty.ptr, n, what)) || (rc = down(rec_slot, h->rec_slot.ptr, n, what)) ||
+      (rc = down(rec_hash, h->rec_hash.ptr, n * h->stride, what)) || (rc = down(rec_hash_len, h->rec_hash_len.ptr, n, what)) ||
+      (rc = down(winner, h->winner.ptr, n, what)))
     return rc;
   if (w[PZ_RS_COUNT] & kRsErrPanic)
     return fail(PZ_EINDEX, "stateRecalc would panic (processCrosslinks' indices or CalculateRewards' CheckBit); the state is as before it");
@@ -434,7 +397,7 @@ int pz_dev_state_recalc(pz_recalc_state* h, pz_att_pool* pool, pz_vote_cache* ca
                         void* stream) {
   int rc = check_call(h, pool, b, d_scratch);
   if (rc) return rc;
-  if ((rc = use_device(h))) return rc;
+  if ((rc = h->use())) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   hipStream_t s = static_cast<hipStream_t>(stream);
   return enqueue(h, pool, cache, *b, d_scratch, s);
@@ -448,19 +411,13 @@ int pz_debug_state_recalc_timed(pz_recalc_state* h, pz_att_pool* pool, pz_vote_c
   int rc = check_call(h, pool, b, d_scratch);
   if (rc) return rc;
   if (!ms) return fail(PZ_EINVAL, "null pointer");
-  if ((rc = use_device(h))) return rc;
+  if ((rc = h->use())) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
-  hipEvent_t ev[8];
-  for (auto& x : ev)
-    if (hipEventCreate(&x) != hipSuccess) return fail(PZ_EDEVICE, "hipEventCreate");
+  Events ev;
+  if ((rc = ev.create(8))) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  rc = enqueue(h, pool, cache, *b, d_scratch, s, ev);
-  hipError_t e = hipStreamSynchronize(s);
   static const int kFrom[6] = {0, 2, 3, 4, 5, 6};
-  for (int k = 0; k < 6 && !rc && e == hipSuccess; ++k) e = hipEventElapsedTime(&ms[k], ev[kFrom[k]], ev[kFrom[k] + 1]);
-  for (auto& x : ev) (void)hipEventDestroy(x);
-  if (rc) return rc;
-  return e == hipSuccess ? PZ_OK : hip_fail(e, "timed state recalc");
+  return ev.elapsed(enqueue(h, pool, cache, *b, d_scratch, s, &ev), ms, kFrom, 6, s, "timed state recalc");
 }
 #endif
 

@@ -2,12 +2,66 @@
 // reads the vote cache's table (votecache.hip) and the pool's live columns and counts (attpool.hip)
 // where they lie.  Not part of the C ABI.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/prysm_hip.h"
+#include "runtime.h"
 
 namespace pz {
+
+// What every resident handle is: a device, a lock, and the stream of its last call, which its
+// reads, its host-pointer forms and its destructor wait for.
+struct Resident {
+  int device = 0;
+  std::mutex mu;
+  hipStream_t last = nullptr;
+  // Before a handle is made: the device checked (gfx950, its context) and current.
+  static int open(int device) {
+    DeviceCtx* c;
+    int rc = device_ctx(device, &c);
+    if (rc) return rc;
+    hipError_t e = hipSetDevice(device);
+    return e == hipSuccess ? PZ_OK : hip_fail(e, "hipSetDevice");
+  }
+  int use() const {
+    hipError_t e = hipSetDevice(device);
+    return e == hipSuccess ? PZ_OK : hip_fail(e, "hipSetDevice");
+  }
+  int wait(const char* what) const {
+    hipError_t e = hipStreamSynchronize(last);
+    return e == hipSuccess ? PZ_OK : hip_fail(e, what);
+  }
+  // Waits for the last call and reads the handle's words (its counts and sticky error word).
+  int settle(void* host, const DevBuf& words, size_t bytes, const char* what) const {
+    int rc = wait(what);
+    return rc ? rc : down(static_cast<uint8_t*>(host), words.ptr, bytes, what);
+  }
+  // A handle's destructor starts here, before it releases what a call in flight may still touch.
+  void drain() const {
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(last);
+  }
+};
+
+// A host-pointer form on a handle, in this order: use the device, lock the handle, wait for its
+// last stream (the staging stream is the library's own, non-blocking: the caller cannot order a
+// call on it against the handle's earlier calls, so the library does), take the device context,
+// lock it, make its stream, hand out a Stager.  rc != PZ_OK: the call ends with it.  A host form
+// of an entry point without a handle (h NULL) is the same from "take the device context" on.
+struct HostForm {
+  int rc;
+  std::unique_lock<std::mutex> handle, ctx;
+  Stager st{nullptr, nullptr};
+  explicit HostForm(Resident* h = nullptr, const char* what = "") {
+    DeviceCtx* c;
+    if (h) {
+      if ((rc = h->use())) return;
+      handle = std::unique_lock<std::mutex>(h->mu);
+      if ((rc = h->wait(what))) return;
+    }
+    if ((rc = h ? device_ctx(h->device, &c) : acquire(&c))) return;
+    ctx = std::unique_lock<std::mutex>(c->mu);
+    if ((rc = c->ensure_stream())) return;
+    st.c = c, st.s = c->stream;
+  }
+};
 
 // The vote cache's lookup side: device pointers, valid for the handle's lifetime.
 struct VcView {

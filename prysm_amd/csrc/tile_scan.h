@@ -19,6 +19,9 @@ namespace {
 constexpr int kTile = 256, kTileWaves = kTile / 64;
 constexpr int kScanThreads = 1024;
 
+inline uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
+inline uint64_t pad256(uint64_t x) { return (x + 255) & ~uint64_t(255); }  // a scratch size
+
 typedef __attribute__((address_space(1))) uint8_t gbyte;
 
 // 16-byte unaligned pieces, the last one overlapping the one before it with the same bytes:

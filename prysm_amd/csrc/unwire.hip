@@ -21,11 +21,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
 #include <vector>
 
+#include "att_cols.h"
 #include "proto3_canon.h"
-#include "runtime.h"
+#include "resident.h"
 #include "tile_scan.h"
 
 namespace pz {
@@ -208,8 +208,6 @@ int att_out_args(const pz_attestation_cols_out* o, uint64_t n, uint32_t field_nu
   return PZ_OK;
 }
 
-uint64_t tiles_of(uint64_t n) { return (n + kTile - 1) / kTile; }
-uint64_t pad256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
 
 hipError_t launch_unwire_att(AttArgs a, uint64_t* totals, void* scratch, hipStream_t s) {
   hipError_t e;
@@ -404,11 +402,9 @@ int pz_unwire_attestations(const uint8_t* bytes, const uint64_t* offsets, uint64
   if ((rc = check_csr(offsets, n, "record"))) return rc;
   if (n && !bytes) return fail(PZ_EINVAL, "bytes is null");
   const uint64_t nbytes = n ? offsets[n] - offsets[0] : 0;
-  DeviceCtx* ctx;
-  if ((rc = acquire(&ctx))) return rc;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if ((rc = ctx->ensure_stream())) return rc;
-  Stager st{ctx, ctx->stream};
+  HostForm f;  // (no handle: the current device's context)
+  if (f.rc) return f.rc;
+  Stager& st = f.st;
   const std::vector<uint64_t> rb = rebase(offsets, n);
   AttArgs a{};
   a.d = st.up(n ? bytes + offsets[0] : nullptr, nbytes);
@@ -418,20 +414,9 @@ int pz_unwire_attestations(const uint8_t* bytes, const uint64_t* offsets, uint64
   a.field = field_num;
   // every column at its bound: bytes columns and sig values the input's byte count, elements half
   pz_attestation_cols_out d{};
-  d.slot = st.up<uint64_t>(nullptr, n);
-  d.shard_id = st.up<uint64_t>(nullptr, n);
-  d.justified_slot = st.up<uint64_t>(nullptr, n);
-  d.justified_block_hash = st.up<uint8_t>(nullptr, nbytes);
-  d.justified_block_hash_offs = st.up<uint64_t>(nullptr, n + 1);
-  d.shard_block_hash = st.up<uint8_t>(nullptr, nbytes);
-  d.shard_block_hash_offs = st.up<uint64_t>(nullptr, n + 1);
-  d.attester_bitfield = st.up<uint8_t>(nullptr, nbytes);
-  d.attester_bitfield_offs = st.up<uint64_t>(nullptr, n + 1);
-  d.oblique_parent_hashes = st.up<uint8_t>(nullptr, nbytes);
-  d.oblique_offs = st.up<uint64_t>(nullptr, nbytes / 2 + 1);
-  d.oblique_first = st.up<uint64_t>(nullptr, n + 1);
-  d.aggregate_sig = st.up<uint64_t>(nullptr, nbytes);
-  d.aggregate_sig_first = st.up<uint64_t>(nullptr, n + 1);
+  const uint64_t bound[kAttTotals] = {nbytes, nbytes, nbytes, nbytes / 2, nbytes, nbytes};
+  for (int k = 0; k < kAttNCols; ++k)
+    att_set_out(&d, k, st.put(nullptr, att_col_len(kAttTable[k], n, bound) * kAttTable[k].width));
   d.n_oblique = out->n_oblique ? st.up<uint64_t>(nullptr, n) : nullptr;
   d.last_byte = out->last_byte ? st.up<uint8_t>(nullptr, n) : nullptr;
   d.status = st.up<int32_t>(nullptr, n);
@@ -442,26 +427,13 @@ int pz_unwire_attestations(const uint8_t* bytes, const uint64_t* offsets, uint64
   st.check(launch_unwire_att(a, d_totals, scratch, st.s), "pz_unwire_att kernels");
   st.down(totals, d_totals, kAttCols);
   if (st.sync()) return st.rc;
-  static const char* const kWhat[6] = {"justified_block_hash", "shard_block_hash", "attester_bitfield",
-                                       "oblique elements",     "oblique bytes",    "aggregate_sig"};
-  for (int c = 0; c < 6; ++c)
+  for (int c = 0; c < kAttTotals; ++c)
     if (totals[c] > caps[c])
-      return fail(PZ_ERANGE, "%s needs %llu, capacity %llu", kWhat[c], (unsigned long long)totals[c],
+      return fail(PZ_ERANGE, "%s needs %llu, capacity %llu", att_total_name(c), (unsigned long long)totals[c],
                   (unsigned long long)caps[c]);
-  st.down(out->slot, d.slot, n);
-  st.down(out->shard_id, d.shard_id, n);
-  st.down(out->justified_slot, d.justified_slot, n);
-  st.down(out->justified_block_hash, d.justified_block_hash, totals[0]);
-  st.down(out->justified_block_hash_offs, d.justified_block_hash_offs, n + 1);
-  st.down(out->shard_block_hash, d.shard_block_hash, totals[1]);
-  st.down(out->shard_block_hash_offs, d.shard_block_hash_offs, n + 1);
-  st.down(out->attester_bitfield, d.attester_bitfield, totals[2]);
-  st.down(out->attester_bitfield_offs, d.attester_bitfield_offs, n + 1);
-  st.down(out->oblique_parent_hashes, d.oblique_parent_hashes, totals[4]);
-  st.down(out->oblique_offs, d.oblique_offs, totals[3] + 1);
-  st.down(out->oblique_first, d.oblique_first, n + 1);
-  st.down(out->aggregate_sig, d.aggregate_sig, totals[5]);
-  st.down(out->aggregate_sig_first, d.aggregate_sig_first, n + 1);
+  for (int k = 0; k < kAttNCols; ++k)
+    st.down(static_cast<uint8_t*>(att_out(*out, k)), static_cast<const uint8_t*>(att_out(d, k)),
+            att_col_len(kAttTable[k], n, totals) * kAttTable[k].width);
   if (out->n_oblique) st.down(out->n_oblique, d.n_oblique, n);
   if (out->last_byte) st.down(out->last_byte, d.last_byte, n);
   st.down(out->status, d.status, n);
@@ -494,11 +466,9 @@ int pz_unwire_blocks(const uint8_t* blocks, const uint64_t* offsets, uint64_t n,
   if ((rc = check_csr(offsets, n, "block"))) return rc;
   if (n && !blocks) return fail(PZ_EINVAL, "blocks is null");
   const uint64_t nbytes = n ? offsets[n] - offsets[0] : 0, base = n ? offsets[0] : 0;
-  DeviceCtx* ctx;
-  if ((rc = acquire(&ctx))) return rc;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if ((rc = ctx->ensure_stream())) return rc;
-  Stager st{ctx, ctx->stream};
+  HostForm f;  // (no handle: the current device's context)
+  if (f.rc) return f.rc;
+  Stager& st = f.st;
   const std::vector<uint64_t> rb = rebase(offsets, n);
   BlockArgs a{};
   a.d = st.up(n ? blocks + base : nullptr, nbytes);

@@ -36,21 +36,17 @@
 #include <mutex>
 #include <vector>
 
+#include "att_cols.h"
 #include "resident.h"
-#include "runtime.h"
 #include "votecache_dev.h"
 #include "votes_dev.h"
 
-struct pz_vote_cache {
-  int device = 0;
+struct pz_vote_cache : pz::Resident {  // (last: read / voters / the host forms wait for it)
   uint64_t nval = 0, words = 0;
   uint32_t slot_cap = 0, cells = 0;
-  std::mutex mu;
-  hipStream_t last = nullptr;  // the stream of the last tally: read / voters wait for it
   pz::DevBuf bitmaps, totals, keys, table, words2;  // words2: nslots (u32) at 0, the error word (u64) at 8
   ~pz_vote_cache() {
-    (void)hipSetDevice(device);
-    (void)hipStreamSynchronize(last);
+    drain();
     for (pz::DevBuf* b : {&bitmaps, &totals, &keys, &table, &words2}) b->release();
   }
 };
@@ -80,8 +76,6 @@ struct VcArgs {
   uint32_t* src_cell;
   uint64_t* mask;
 };
-
-constexpr uint64_t r16(uint64_t x) { return (x + 15) & ~15ull; }
 
 #define PZ_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
@@ -317,7 +311,7 @@ uint64_t scratch_bytes(uint64_t natt, uint64_t nsrc) { return 16 + r16(nsrc) + 2
 
 // The four launches (and the memset of the flags and used[]) on s.  ev (the A/B library's timed
 // entry; null in the product): five events, one before the first launch and one after each.
-int enqueue(pz_vote_cache* h, const pz_vote_cols_batch& b, void* d_scratch, hipStream_t s, hipEvent_t* ev = nullptr) {
+int enqueue(pz_vote_cache* h, const pz_vote_cols_batch& b, void* d_scratch, hipStream_t s, Events* ev = nullptr) {
   VcArgs a;
   std::memset(&a, 0, sizeof a);
   a.b = b;
@@ -339,38 +333,29 @@ int enqueue(pz_vote_cache* h, const pz_vote_cols_batch& b, void* d_scratch, hipS
   if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
   h->last = s;
   const uint32_t wave_blocks = (uint32_t)((b.natt * 64 + kThreads - 1) / kThreads);
-  auto stamp = [&](int k) {
-    if (ev) (void)hipEventRecord(ev[k], s);
-  };
-  stamp(0);
+  stamp(ev, 0, s);
   hipLaunchKernelGGL(pz_vc_mark_kernel, dim3(wave_blocks), dim3(kThreads), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_vc_mark_kernel");
-  stamp(1);
+  stamp(ev, 1, s);
   if (a.nsrc) {
     hipLaunchKernelGGL(pz_vc_intern_kernel, dim3((uint32_t)((a.nsrc + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_vc_intern_kernel");
   }
-  stamp(2);
+  stamp(ev, 2, s);
   hipLaunchKernelGGL(pz_vc_commit_kernel, dim3(1), dim3(kCommitThreads), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_vc_commit_kernel");
-  stamp(3);
+  stamp(ev, 3, s);
   hipLaunchKernelGGL(pz_vc_tally_kernel, dim3(64 * wave_blocks), dim3(kThreads), 0, s, a);
   if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_vc_tally_kernel");
-  stamp(4);
+  stamp(ev, 4, s);
   return PZ_OK;
-}
-
-int use_device(pz_vote_cache* h) {
-  hipError_t e = hipSetDevice(h->device);
-  return e == hipSuccess ? PZ_OK : hip_fail(e, "hipSetDevice");
 }
 
 // Waits for the last tally and reads nslots and the sticky error word; the code to report.
 int settle(pz_vote_cache* h, uint32_t* nslots, int* sticky) {
-  hipError_t e = hipStreamSynchronize(h->last);
   uint64_t w[2] = {0, 0};
-  if (e == hipSuccess) e = hipMemcpy(w, h->words2.ptr, sizeof w, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return hip_fail(e, "vote cache read");
+  int rc = h->settle(w, h->words2, sizeof w, "vote cache read");
+  if (rc) return rc;
   *nslots = (uint32_t)w[0];
   *sticky = (w[1] & kVcErrPanic)      ? PZ_EINDEX
             : (w[1] & kVcErrCapacity) ? PZ_ERANGE
@@ -395,7 +380,7 @@ int check_lookup(const pz_vote_cache* h, const uint8_t* hashes, uint64_t n, cons
 
 int enqueue_lookup(pz_vote_cache* h, const uint8_t* d_hashes, uint64_t n, uint64_t* d_totals, uint32_t* d_slots,
                    hipStream_t s) {
-  if (reinterpret_cast<uintptr_t>(d_hashes) & 15) return fail(PZ_EINVAL, "lookup: hashes must be 16-B aligned");
+  if (!aligned16(d_hashes)) return fail(PZ_EINVAL, "lookup: hashes must be 16-B aligned");
   VcLookupArgs a;
   a.table = static_cast<const uint32_t*>(h->table.ptr);
   a.keys = static_cast<const uint8_t*>(h->keys.ptr);
@@ -435,7 +420,7 @@ int pz_dev_vote_cache_lookup(pz_vote_cache* h, const uint8_t* d_hashes, uint64_t
                              void* stream) {
   int rc = check_lookup(h, d_hashes, n, d_totals);
   if (rc) return rc < 0 ? rc : PZ_OK;
-  if ((rc = use_device(h))) return rc;
+  if ((rc = h->use())) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   return enqueue_lookup(h, d_hashes, n, d_totals, d_slots, static_cast<hipStream_t>(stream));
 }
@@ -443,15 +428,9 @@ int pz_dev_vote_cache_lookup(pz_vote_cache* h, const uint8_t* d_hashes, uint64_t
 int pz_vote_cache_lookup(pz_vote_cache* h, const uint8_t* hashes, uint64_t n, uint64_t* totals, uint32_t* slots) {
   int rc = check_lookup(h, hashes, n, totals);
   if (rc) return rc < 0 ? rc : PZ_OK;
-  if ((rc = use_device(h))) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  hipError_t e = hipStreamSynchronize(h->last);  // the staging stream is not the last tally's
-  if (e != hipSuccess) return hip_fail(e, "vote cache lookup");
-  DeviceCtx* c;
-  if ((rc = device_ctx(h->device, &c))) return rc;
-  std::lock_guard<std::mutex> lc(c->mu);
-  if ((rc = c->ensure_stream())) return rc;
-  Stager st{c, c->stream};
+  HostForm f(h, "vote cache lookup");  // (the staging stream is not the last tally's: it waits)
+  if (f.rc) return f.rc;
+  Stager& st = f.st;
   const uint8_t* d_hashes = st.up(hashes, n * 32);
   uint64_t* d_totals = st.up<uint64_t>(nullptr, n);
   uint32_t* d_slots = slots ? st.up<uint32_t>(nullptr, n) : nullptr;
@@ -468,11 +447,9 @@ int pz_vote_cache_new(uint64_t nval, uint32_t slot_cap, int device, pz_vote_cach
   if (nval > PZ_MAX_VALIDATORS) return fail(PZ_ETOOMANY, "validator count %llu above MaxValidators", (unsigned long long)nval);
   if (nval == 0 || slot_cap == 0 || slot_cap > kVcMaxSlotCap)
     return fail(PZ_EINVAL, "vote cache of %llu validators and %u slots", (unsigned long long)nval, slot_cap);
-  DeviceCtx* dc;
-  int rc = device_ctx(device, &dc);
+  int rc = Resident::open(device);
   if (rc) return rc;
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  hipError_t e;
   auto* h = new pz_vote_cache();
   h->device = device;
   h->nval = nval;
@@ -480,21 +457,12 @@ int pz_vote_cache_new(uint64_t nval, uint32_t slot_cap, int device, pz_vote_cach
   h->slot_cap = slot_cap;
   h->cells = vc_cells(slot_cap);
   const size_t bm = (size_t)slot_cap * h->words * 4;
-  if ((rc = h->bitmaps.reserve(bm)) || (rc = h->totals.reserve((size_t)slot_cap * 8)) ||
-      (rc = h->keys.reserve((size_t)slot_cap * 32)) || (rc = h->table.reserve((size_t)h->cells * 4)) ||
-      (rc = h->words2.reserve(16))) {
+  const char* what = "vote cache init";
+  if ((rc = h->bitmaps.fill(bm, 0, what)) || (rc = h->totals.fill((size_t)slot_cap * 8, 0, what)) ||
+      (rc = h->keys.fill((size_t)slot_cap * 32, 0, what)) || (rc = h->table.fill((size_t)h->cells * 4, 0xFF, what)) ||
+      (rc = h->words2.fill(16, 0, what)) || ((e = hipDeviceSynchronize()) != hipSuccess && (rc = hip_fail(e, what)))) {
     delete h;
     return rc;
-  }
-  e = hipMemset(h->bitmaps.ptr, 0, bm);
-  if (e == hipSuccess) e = hipMemset(h->totals.ptr, 0, (size_t)slot_cap * 8);
-  if (e == hipSuccess) e = hipMemset(h->keys.ptr, 0, (size_t)slot_cap * 32);
-  if (e == hipSuccess) e = hipMemset(h->table.ptr, 0xFF, (size_t)h->cells * 4);
-  if (e == hipSuccess) e = hipMemset(h->words2.ptr, 0, 16);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    delete h;
-    return hip_fail(e, "vote cache init");
   }
   *out = h;
   return PZ_OK;
@@ -509,8 +477,8 @@ uint64_t pz_vote_cache_scratch_bytes(uint64_t natt, uint64_t n_recent, uint64_t 
 int pz_dev_vote_cache_tally(pz_vote_cache* h, const pz_vote_cols_batch* b, void* d_scratch, void* stream) {
   int rc = check_args(h, b);
   if (rc) return rc < 0 ? rc : PZ_OK;
-  if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15)) return fail(PZ_EINVAL, "d_scratch must be a 16-B aligned device pointer");
-  if ((rc = use_device(h))) return rc;
+  if (!d_scratch || !aligned16(d_scratch)) return fail(PZ_EINVAL, "d_scratch must be a 16-B aligned device pointer");
+  if ((rc = h->use())) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   return enqueue(h, *b, d_scratch, static_cast<hipStream_t>(stream));
 }
@@ -523,17 +491,12 @@ int pz_debug_vote_cache_tally_timed(pz_vote_cache* h, const pz_vote_cols_batch* 
   int rc = check_args(h, b);
   if (rc) return rc < 0 ? rc : PZ_OK;
   if (!d_scratch || !ms) return fail(PZ_EINVAL, "null pointer");
-  if ((rc = use_device(h))) return rc;
+  if ((rc = h->use())) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
-  hipEvent_t ev[5];
-  for (auto& x : ev)
-    if (hipEventCreate(&x) != hipSuccess) return fail(PZ_EDEVICE, "hipEventCreate");
-  rc = enqueue(h, *b, d_scratch, static_cast<hipStream_t>(stream), ev);
-  hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
-  for (int k = 0; k < 4 && !rc && e == hipSuccess; ++k) e = hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
-  for (auto& x : ev) (void)hipEventDestroy(x);
-  if (rc) return rc;
-  return e == hipSuccess ? PZ_OK : hip_fail(e, "timed vote cache tally");
+  Events ev;
+  if ((rc = ev.create(5))) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return ev.elapsed(enqueue(h, *b, d_scratch, s, &ev), ms, nullptr, 4, s, "timed vote cache tally");
 }
 #endif
 
@@ -546,24 +509,19 @@ int pz_vote_cache_tally(pz_vote_cache* h, const pz_vote_cols_batch* hb) {
     if ((rc = check_csr(hb->oblique_first, n, "oblique_first")) || (rc = check_csr(hb->oblique_offs, ne, "oblique"))) return rc;
     if (hb->oblique_first[n] > ne) return fail(PZ_EINVAL, "oblique_first reaches past n_oblique_total");
   }
-  if ((rc = use_device(h))) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  DeviceCtx* c;
-  if ((rc = device_ctx(h->device, &c))) return rc;
-  std::lock_guard<std::mutex> lc(c->mu);
-  if ((rc = c->ensure_stream())) return rc;
-  Stager st{c, c->stream};
+  HostForm f(h, "vote cache tally");
+  if (f.rc) return f.rc;
+  Stager& st = f.st;
   pz_vote_cols_batch d = *hb;
   if (hb->n_oblique) d.n_oblique = st.up(hb->n_oblique, n);
-  if (hb->oblique_first) {
-    d.oblique_parent_hashes = st.up(hb->oblique_parent_hashes, hb->oblique_offs[ne]);
-    d.oblique_offs = st.up(hb->oblique_offs, ne + 1);
-    d.oblique_first = st.up(hb->oblique_first, n + 1);
-  } else {
-    d.oblique_parent_hashes = nullptr, d.oblique_offs = nullptr;
-  }
-  d.bits = st.up(hb->bits, hb->boffs[n]);
-  d.boffs = st.up(hb->boffs, n + 1);
+  pz_attestation_cols hc{}, dc;  // the batch's attestation columns under their pz_attestation_cols names
+  hc.oblique_parent_hashes = hb->oblique_parent_hashes, hc.oblique_offs = hb->oblique_offs, hc.oblique_first = hb->oblique_first;
+  hc.attester_bitfield = hb->bits, hc.attester_bitfield_offs = hb->boffs;
+  uint64_t staged[kAttTotals];
+  stage_att_cols(st, hc, n, kAttObliqueCols | kAttBitsCols, &dc, staged);
+  d.oblique_parent_hashes = dc.oblique_parent_hashes, d.oblique_offs = dc.oblique_offs, d.oblique_first = dc.oblique_first;
+  d.n_oblique_total = staged[kTotElems];  // the sources are the elements the rows name
+  d.bits = dc.attester_bitfield, d.boffs = dc.attester_bitfield_offs;
   d.status = st.up(hb->status, n);
   d.committee = st.up(hb->committee, n);
   d.parents_start = st.up(hb->parents_start, n);
@@ -572,7 +530,7 @@ int pz_vote_cache_tally(pz_vote_cache* h, const pz_vote_cols_batch* hb) {
   d.members = st.up(hb->members, hb->coffs[hb->ncomm]);
   d.coffs = st.up(hb->coffs, hb->ncomm + 1);
   d.balance = st.up(hb->balance, h->nval);
-  uint8_t* scr = st.up<uint8_t>(nullptr, scratch_bytes(n, hb->n_recent + ne));
+  uint8_t* scr = st.up<uint8_t>(nullptr, scratch_bytes(n, hb->n_recent + d.n_oblique_total));
   if (st.rc) return st.rc;
   if ((rc = enqueue(h, d, scr, st.s))) return rc;
   return st.sync();
@@ -580,7 +538,7 @@ int pz_vote_cache_tally(pz_vote_cache* h, const pz_vote_cols_batch* hb) {
 
 int pz_vote_cache_read(pz_vote_cache* h, uint8_t* hashes, uint64_t* totals, uint64_t cap, uint64_t* count) {
   if (!h || !count) return fail(PZ_EINVAL, "vote cache / count is null");
-  int rc = use_device(h);
+  int rc = h->use();
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   uint32_t ns;
@@ -598,7 +556,7 @@ int pz_vote_cache_read(pz_vote_cache* h, uint8_t* hashes, uint64_t* totals, uint
 
 int pz_vote_cache_voters(pz_vote_cache* h, const uint8_t hash[32], uint32_t* words, int* present) {
   if (!h || !hash || !present) return fail(PZ_EINVAL, "vote cache / hash / present is null");
-  int rc = use_device(h);
+  int rc = h->use();
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   uint32_t ns;

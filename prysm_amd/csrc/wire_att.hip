@@ -25,11 +25,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <mutex>
-#include <vector>
 
+#include "att_cols.h"
 #include "proto3_canon.h"  // put_varint
-#include "runtime.h"
+#include "resident.h"
 
 namespace pz {
 namespace {
@@ -803,15 +802,11 @@ int att_args(const pz_attestation_cols* c, uint64_t n, uint32_t field_num, AttAr
   if (!c) return fail(PZ_EINVAL, "columns are null");
   if (field_num >= (1u << 29)) return fail(PZ_EINVAL, "field number %u out of range", field_num);
   *a = AttArgs{};
-  a->col[0] = c->slot;
-  a->col[1] = c->shard_id;
-  a->col[2] = c->justified_slot;
-  a->bdat[0] = c->justified_block_hash;
-  a->boff[0] = c->justified_block_hash_offs;
-  a->bdat[1] = c->shard_block_hash;
-  a->boff[1] = c->shard_block_hash_offs;
-  a->bdat[2] = c->attester_bitfield;
-  a->boff[2] = c->attester_bitfield_offs;
+  for (int k = 0; k < 3; ++k) {  // the three scalars, the three bytes columns
+    a->col[k] = static_cast<const uint64_t*>(att_in(*c, k));
+    a->bdat[k] = static_cast<const uint8_t*>(att_in(*c, kAttRanges[k][0]));
+    a->boff[k] = static_cast<const uint64_t*>(att_in(*c, kAttRanges[k][1]));
+  }
   a->odat = c->oblique_parent_hashes;
   a->ooff = c->oblique_offs;
   a->ofirst = c->oblique_first;
@@ -875,42 +870,18 @@ int pz_wire_attestations(const pz_attestation_cols* c, uint64_t n, uint32_t fiel
     if (a.boff[k] && (rc = check_csr(a.boff[k], n, "bytes column"))) return rc;
   if (a.ofirst && (rc = check_csr(a.ofirst, n, "oblique ranges"))) return rc;
   if (a.sfirst && (rc = check_csr(a.sfirst, n, "signature ranges"))) return rc;
-  const uint64_t ne = a.ofirst ? c->oblique_first[n] : 0, ns = a.sfirst ? c->aggregate_sig_first[n] : 0;
+  const uint64_t ne = a.ofirst ? c->oblique_first[n] : 0;
   if (a.ofirst && c->oblique_first[0] != 0) return fail(PZ_EINVAL, "oblique ranges must start at 0");
   if (a.sfirst && c->aggregate_sig_first[0] != 0) return fail(PZ_EINVAL, "signature ranges must start at 0");
   if (ne && (rc = check_csr(c->oblique_offs, ne, "oblique elements"))) return rc;
-  DeviceCtx* ctx;
-  if ((rc = acquire(&ctx))) return rc;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if ((rc = ctx->ensure_stream())) return rc;
-  Stager st{ctx, ctx->stream};
-  uint64_t bytes_total = 0;
-  std::vector<uint64_t> rb[3];
-  for (int k = 0; k < 3; ++k) {
-    if (a.col[k]) a.col[k] = st.up(a.col[k], n);
-    if (a.boff[k]) {
-      rb[k] = rebase(a.boff[k], n);
-      a.bdat[k] = st.up(a.bdat[k] + a.boff[k][0], rb[k][n]);
-      a.boff[k] = st.up(rb[k].data(), n + 1);
-      bytes_total += rb[k][n];
-    }
-  }
-  std::vector<uint64_t> oo;
-  if (a.ofirst) {
-    a.ofirst = st.up(a.ofirst, n + 1);
-    if (ne) {
-      oo = rebase(c->oblique_offs, ne);
-      a.odat = st.up(c->oblique_parent_hashes + c->oblique_offs[0], oo[ne]);
-      a.ooff = st.up(oo.data(), ne + 1);
-      bytes_total += oo[ne];
-    } else {
-      a.ooff = st.up(c->oblique_offs, 1);
-    }
-  }
-  if (a.sfirst) {
-    a.sfirst = st.up(a.sfirst, n + 1);
-    a.sig = st.up(c->aggregate_sig, std::max<uint64_t>(ns, 1));
-  }
+  HostForm f;  // (no handle: the current device's context)
+  if (f.rc) return f.rc;
+  Stager& st = f.st;
+  pz_attestation_cols d;
+  uint64_t up[kAttTotals];
+  if (stage_att_cols(st, *c, n, kAttAllCols, &d, up)) return st.rc;
+  (void)att_args(&d, n, field_num, &a);  // (the launch's form of the staged columns; *c passed these checks above)
+  const uint64_t bytes_total = up[kTotJbh] + up[kTotSbh] + up[kTotBits] + up[kTotElemBytes], ns = up[kTotSigs];
   void* scratch = st.up<uint8_t>(nullptr, pz_wire_attestations_scratch_bytes(n));
   a.offs = st.zeros<uint64_t>(n + 1);
   a.out = st.up<uint8_t>(nullptr, pz_wire_attestations_bound(n, bytes_total, ne, ns));

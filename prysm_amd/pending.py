@@ -20,7 +20,6 @@ from prysm_amd._lib import lib
 CAPS = ("rows", "justified_block_hash", "shard_block_hash", "attester_bitfield", "oblique_elements", "oblique_bytes",
         "aggregate_sig")  # pz_att_pool_new's caps[7] / pz_att_pool_counts' counts[7]
 _BYTES = ("justified_block_hash", "shard_block_hash", "attester_bitfield", "oblique_parent_hashes")
-_STICKY = (_lib.PZ_EINVAL, _lib.PZ_ERANGE)
 
 
 class _Raw:
@@ -30,29 +29,22 @@ class _Raw:
         self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
 
 
-class DevicePendingAttestations:
+class DevicePendingAttestations(_lib.Handle):
     """``caps``: the seven capacities (``CAPS``' order), fixed for the pool's lifetime.  A call that
     would exceed one changes nothing (PZ_ERANGE, sticky); a kept row with an inverted range lands
     empty (PZ_EINVAL, sticky).  Every read raises the sticky error; ``strict=False`` returns what the
     pool holds regardless."""
+    _FREE = "pz_att_pool_free"
+    _STICKY = (_lib.PZ_EINVAL, _lib.PZ_ERANGE)
 
     def __init__(self, caps, device=0):
         self.caps = np.ascontiguousarray(caps, dtype=np.uint64)
         assert self.caps.shape == (7,)
-        self._h = _lib.ctypes.c_void_p()
-        lib.call("pz_att_pool_new", self.caps.ctypes.data, device, _lib.ctypes.byref(self._h))
+        self._new("pz_att_pool_new", self.caps.ctypes.data, device)
         self.device = device
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            lib.dll.pz_att_pool_free(h)
-            self._h = None
-
     def _stream(self):
-        import torch
-
-        return _lib.ctypes.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+        return _lib.stream_ptr(self.device)
 
     # ---- writes ------------------------------------------------------------------------------
     def append_columns(self, cols, n, status, committee, take=None):
@@ -63,30 +55,15 @@ class DevicePendingAttestations:
         stream, asynchronous (``pz_dev_att_pool_append``)."""
         import torch
 
-        dev = status.device
-        one = torch.zeros(1, dtype=torch.uint8, device=dev)  # (a bytes column with no byte still needs an address)
-        ptrs = []
-        for k in wire.ATT_COLS:
-            v = cols.get(k)
-            if v is not None and not v.numel() and (k in _BYTES or k == "aggregate_sig"):
-                v = one
-            ptrs.append(v.data_ptr() if v is not None and v.numel() else None)
-        c = _lib.AttestationCols(*ptrs)
-        scratch = torch.empty(max(int(lib.dll.pz_att_pool_scratch_bytes(n)), 16), dtype=torch.uint8, device=dev)
-        p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        c = _lib.att_cols(cols)
+        scratch = torch.empty(max(int(lib.dll.pz_att_pool_scratch_bytes(n)), 16), dtype=torch.uint8, device=status.device)
+        p = _lib.dptr
         lib.call("pz_dev_att_pool_append", self._h, _lib.ctypes.byref(c), n, p(status), p(committee), p(take),
                  scratch.data_ptr(), self._stream())
 
     def append_host(self, cols, n, status, committee, take=None):
         """The same append over host arrays (numpy; ``pz_att_pool_append``, synchronous)."""
-        keep = {k: np.ascontiguousarray(cols[k]) for k in wire.ATT_COLS if cols.get(k) is not None}
-        one = np.zeros(1, dtype=np.uint8)
-        for k in _BYTES:
-            if k in keep and not keep[k].size:
-                keep[k] = one
-        if "aggregate_sig" in keep and not keep["aggregate_sig"].size:
-            keep["aggregate_sig"] = np.zeros(1, dtype=np.uint64)
-        c = _lib.AttestationCols(**{k: v.ctypes.data for k, v in keep.items()})
+        c = _lib.att_cols(cols)
         status = np.ascontiguousarray(status, dtype=np.int32)
         committee = np.ascontiguousarray(committee, dtype=np.uint32)
         take = None if take is None else np.ascontiguousarray(take, dtype=np.uint8)
@@ -99,10 +76,6 @@ class DevicePendingAttestations:
         lib.call("pz_dev_att_pool_prune", self._h, int(last_state_recalc), self._stream())
 
     # ---- reads -------------------------------------------------------------------------------
-    def _rc(self, rc, strict):
-        if rc != _lib.PZ_OK and (strict or rc not in _STICKY):
-            raise _lib.PzError(rc, lib.dll.pz_last_error().decode())
-
     def counts(self, strict=True):
         """The seven counts (``CAPS``' order) as a uint64 array; waits for the last call."""
         out = np.zeros(7, dtype=np.uint64)
@@ -149,15 +122,12 @@ class DevicePendingAttestations:
         """Everything the pool holds as numpy arrays keyed as ``wire.ATT_COLS``, plus ``committee``
         (``pz_att_pool_read``)."""
         n = self.counts(strict=False)
-        rows, jb, sb, bf, ne, eb, ns = (int(x) for x in n)
-        size = {k: rows for k in wire.ATT_COLS}
-        size.update({k: rows + 1 for k in wire.ATT_COLS if k.endswith("_offs") or k.endswith("_first")})
-        size.update(justified_block_hash=jb, shard_block_hash=sb, attester_bitfield=bf, oblique_parent_hashes=eb,
-                    oblique_offs=ne + 1, aggregate_sig=ns)
+        rows = int(n[0])
+        size = wire.att_sizes(rows, n[1:])
         cols = {k: np.zeros(max(size[k], 1), dtype=np.uint8 if k in _BYTES else np.uint64) for k in wire.ATT_COLS}
         committee = np.zeros(max(rows, 1), dtype=np.uint32)
         out = _lib.AttestationColsOut(*[cols[k].ctypes.data for k in wire.ATT_COLS], None, None, None)
-        caps = np.array([jb, sb, bf, ne, eb, ns], dtype=np.uint64)
+        caps = np.ascontiguousarray(n[1:])
         self._rc(lib.dll.pz_att_pool_read(self._h, _lib.ctypes.byref(out), committee.ctypes.data, caps.ctypes.data), strict)
         res = {k: v[:size[k]] for k, v in cols.items()}
         res["committee"] = committee[:rows]
@@ -230,15 +200,11 @@ class DevicePendingAttestations:
         return b
 
 
-class RecalcState:
-    """The CrystallizedState ``blockchain.state_recalc_device`` advances: ``balance``, ``start`` and
-    ``end`` (the validators' Balance / StartDynasty / EndDynasty) as int64 device tensors, the
-    committees as a device CSR (``members`` int32, ``coffs`` int64), the host scalars and the
-    crosslink records (``pb.CrosslinkRecord``)."""
+class _DeviceValidators:
+    """What both recalc states put on the device: ``balance``, ``start`` and ``end`` as int64
+    tensors and the committees as a CSR (``members`` int32, ``coffs`` int64)."""
 
-    def __init__(self, balance, start_dynasty, end_dynasty, members, coffs, crosslink_records, *, last_state_recalc=0,
-                 justified_streak=0, last_justified_slot=0, last_finalized_slot=0, current_dynasty=1, total_deposits=0,
-                 device=0):
+    def _put_validators(self, balance, start_dynasty, end_dynasty, members, coffs, device):
         import torch
 
         from prysm_amd.blockchain import _to_device
@@ -250,10 +216,6 @@ class RecalcState:
         members = np.ascontiguousarray(members, dtype=np.uint32)
         self.members = _to_device(members if members.size else np.zeros(1, np.uint32), dev)
         self.coffs = u64(coffs)
-        self.crosslink_records = [pb.CrosslinkRecord(r.dynasty, bytes(r.blockhash), r.slot) for r in crosslink_records]
-        self.last_state_recalc, self.justified_streak = int(last_state_recalc), int(justified_streak)
-        self.last_justified_slot, self.last_finalized_slot = int(last_justified_slot), int(last_finalized_slot)
-        self.current_dynasty, self.total_deposits = int(current_dynasty), int(total_deposits)
 
     @property
     def nval(self):
@@ -263,7 +225,23 @@ class RecalcState:
         return self.balance.cpu().numpy().view(np.uint64)
 
 
-class ResidentRecalcState:
+class RecalcState(_DeviceValidators):
+    """The CrystallizedState ``blockchain.state_recalc_device`` advances: ``balance``, ``start`` and
+    ``end`` (the validators' Balance / StartDynasty / EndDynasty) as int64 device tensors, the
+    committees as a device CSR (``members`` int32, ``coffs`` int64), the host scalars and the
+    crosslink records (``pb.CrosslinkRecord``)."""
+
+    def __init__(self, balance, start_dynasty, end_dynasty, members, coffs, crosslink_records, *, last_state_recalc=0,
+                 justified_streak=0, last_justified_slot=0, last_finalized_slot=0, current_dynasty=1, total_deposits=0,
+                 device=0):
+        self._put_validators(balance, start_dynasty, end_dynasty, members, coffs, device)
+        self.crosslink_records = [pb.CrosslinkRecord(r.dynasty, bytes(r.blockhash), r.slot) for r in crosslink_records]
+        self.last_state_recalc, self.justified_streak = int(last_state_recalc), int(justified_streak)
+        self.last_justified_slot, self.last_finalized_slot = int(last_justified_slot), int(last_finalized_slot)
+        self.current_dynasty, self.total_deposits = int(current_dynasty), int(total_deposits)
+
+
+class ResidentRecalcState(_DeviceValidators, _lib.Handle):
     """The CrystallizedState ``blockchain.state_recalc_resident`` advances, resident on one device
     (``pz_recalc_state``, prysm_amd/csrc/recalc.hip): ``RecalcState``'s constructor arguments plus
     ``hash_stride`` (the bytes a crosslink record's hash may take, a multiple of 16 in [32, 256]).
@@ -272,23 +250,16 @@ class ResidentRecalcState:
     reference (PZ_EINDEX) is sticky and raised by every read; ``strict=False`` returns what the
     handle holds -- the state before the panicking call -- regardless."""
 
+    _FREE = "pz_recalc_state_free"
+    _STICKY = (_lib.PZ_EINDEX,)
     _SCALARS = ("last_state_recalc", "justified_streak", "last_justified_slot", "last_finalized_slot", "current_dynasty",
                 "total_deposits")
 
     def __init__(self, balance, start_dynasty, end_dynasty, members, coffs, crosslink_records, *, last_state_recalc=0,
                  justified_streak=0, last_justified_slot=0, last_finalized_slot=0, current_dynasty=1, total_deposits=0,
                  device=0, hash_stride=32):
-        import torch
-
-        from prysm_amd.blockchain import _to_device
-
-        dev = torch.device("cuda", device)
-        u64 = lambda a: _to_device(np.ascontiguousarray(a, dtype=np.uint64), dev)  # noqa: E731
-        self.device, self.hash_stride = device, int(hash_stride)
-        self.balance, self.start, self.end = u64(balance), u64(start_dynasty), u64(end_dynasty)
-        members = np.ascontiguousarray(members, dtype=np.uint32)
-        self.members = _to_device(members if members.size else np.zeros(1, np.uint32), dev)
-        self.coffs = u64(coffs)
+        self._put_validators(balance, start_dynasty, end_dynasty, members, coffs, device)
+        self.hash_stride = int(hash_stride)
         recs = list(crosslink_records)
         self.nrec = len(recs)
         scalars = np.zeros(_lib.RS_COUNT, dtype=np.uint64)
@@ -299,22 +270,8 @@ class ResidentRecalcState:
         offs = np.zeros(self.nrec + 1, dtype=np.uint64)
         offs[1:] = np.cumsum([len(r.blockhash) for r in recs], dtype=np.uint64)
         data = np.frombuffer(b"".join(bytes(r.blockhash) for r in recs), dtype=np.uint8)
-        self._h = _lib.ctypes.c_void_p()
-        lib.call("pz_recalc_state_new", self.nrec, self.hash_stride, scalars.ctypes.data, _lib.ptr(dyn), _lib.ptr(slot),
-                 _lib.ptr(data), offs.ctypes.data, device, _lib.ctypes.byref(self._h))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            lib.dll.pz_recalc_state_free(h)
-            self._h = None
-
-    @property
-    def nval(self):
-        return int(self.balance.numel())
-
-    def balances(self):
-        return self.balance.cpu().numpy().view(np.uint64)
+        self._new("pz_recalc_state_new", self.nrec, self.hash_stride, scalars.ctypes.data, _lib.ptr(dyn), _lib.ptr(slot),
+                  _lib.ptr(data), offs.ctypes.data, device)
 
     def read(self, strict=True):
         """``{"scalars": uint64[8], "rec_dynasty", "rec_slot", "rec_hash" (nrec, hash_stride) uint8,
@@ -325,8 +282,7 @@ class ResidentRecalcState:
                "rec_hash_len": np.zeros(n, np.uint32), "winner": np.full(n, 0xFFFFFFFF, np.uint32)}
         rc = lib.dll.pz_recalc_state_read(self._h, *[out[k].ctypes.data for k in
                                                      ("scalars", "rec_dynasty", "rec_slot", "rec_hash", "rec_hash_len", "winner")])
-        if rc != _lib.PZ_OK and (strict or rc != _lib.PZ_EINDEX):
-            raise _lib.PzError(rc, lib.dll.pz_last_error().decode())
+        self._rc(rc, strict)
         return {k: (v if k == "scalars" else v[:self.nrec]) for k, v in out.items()}
 
     def scalar(self, index, strict=True):

@@ -118,8 +118,7 @@ def attestation_keys_columns(cols, n, out_bytes=32):
     """``Key()`` (attestation.go:61-77) of n records held as host columns (numpy arrays keyed as
     ``wire.ATT_COLS``; see ``wire.attestation_columns``): ``pz_attestation_keys`` assembles and
     hashes the key bytes on the GPU, one lane per record.  Returns (n, out_bytes) uint8."""
-    keep = {k: np.ascontiguousarray(cols[k]) for k in _KEY_COLS if cols.get(k) is not None}
-    c = _lib.AttestationCols(**{k: v.ctypes.data for k, v in keep.items()})
+    c = _lib.att_cols(cols, _KEY_COLS)
     out = np.zeros((n, out_bytes), dtype=np.uint8)
     _lib.lib.call("pz_attestation_keys", _lib.ctypes.byref(c), n, out.ctypes.data if n else None, out_bytes)
     return out
@@ -134,11 +133,11 @@ def attestation_keys_device(cols, n, rec_status=None, out_bytes=32):
     import torch
 
     dev = next(v for v in cols.values() if hasattr(v, "data_ptr")).device
-    c = _lib.AttestationCols(**{k: cols[k].data_ptr() for k in _KEY_COLS if cols.get(k) is not None})
+    c = _lib.att_cols(cols, _KEY_COLS)
     out = torch.empty((n, out_bytes), dtype=torch.uint8, device=dev)
     _lib.lib.call("pz_dev_attestation_keys", _lib.ctypes.byref(c), n,
                   rec_status.data_ptr() if rec_status is not None else None, out.data_ptr() if n else None,
-                  out_bytes, _lib.ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                  out_bytes, _lib.stream_ptr(dev))
     return out
 
 

@@ -70,7 +70,7 @@ class VoteCache:
 _COL_KEYS = ("oblique_parent_hashes", "oblique_offs", "oblique_first")
 
 
-class DeviceVoteCache:
+class DeviceVoteCache(_lib.Handle):
     """The block vote cache resident on one device (``pz_vote_cache``, prysm_amd/csrc/votecache.hip):
     the map from hash to slot lives there too, so a tally takes the decoder's columns
     (``wire.ATT_COLS`` keys) and the checks' outputs as they are -- no work list, no host hash map.
@@ -83,18 +83,23 @@ class DeviceVoteCache:
     The read side is ``VoteCache``'s: ``items()``, ``voters(h)``, ``total(h)``, ``h in cache``.  A
     panic of the reference (PZ_EINDEX) or a call dropped for capacity (PZ_ERANGE) is sticky and
     raised by every read; ``strict=False`` returns what the cache holds regardless."""
+    _FREE = "pz_vote_cache_free"
+    _STICKY = (_lib.PZ_EINDEX, _lib.PZ_ERANGE)
 
     def __init__(self, nval, slot_cap, device=0):
-        self._h = _lib.ctypes.c_void_p()
-        lib.call("pz_vote_cache_new", nval, slot_cap, device, _lib.ctypes.byref(self._h))
+        self._new("pz_vote_cache_new", nval, slot_cap, device)
         self.nval, self.slot_cap, self.device = nval, slot_cap, device
         self.words = (nval + 31) // 32
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            lib.dll.pz_vote_cache_free(h)
-            self._h = None
+    @staticmethod
+    def _batch(cols, have_obl, **members):
+        """``VoteColsBatch`` with the bitfield and (``have_obl``) the oblique columns of ``cols``."""
+        c = _lib.att_cols(cols, ("attester_bitfield", "attester_bitfield_offs") + (_COL_KEYS if have_obl else ()))
+        b = _lib.VoteColsBatch(bits=c.attester_bitfield, boffs=c.attester_bitfield_offs,
+                               oblique_parent_hashes=c.oblique_parent_hashes, oblique_offs=c.oblique_offs,
+                               oblique_first=c.oblique_first, **members)
+        b._keep = c
+        return b
 
     def tally_columns(self, cols, n, status, committee, parents_start, recent, members, coffs, balance, take=None,
                       n_oblique_total=None):
@@ -109,45 +114,34 @@ class DeviceVoteCache:
         import torch
 
         dev = status.device
-        one = torch.zeros(1, dtype=torch.uint8, device=dev)  # (a bytes column with no byte still needs an address)
-        cols = {k: one if k in ("attester_bitfield", "oblique_parent_hashes") and v is not None and not v.numel() else v
-                for k, v in cols.items()}
-        obl = {k: cols.get(k) for k in _COL_KEYS}
-        have_obl = all(v is not None for v in obl.values())
+        have_obl = all(cols.get(k) is not None for k in _COL_KEYS)
         if n_oblique_total is None:
-            n_oblique_total = max(int(obl["oblique_offs"].numel()) - 1, 0) if have_obl else 0
+            n_oblique_total = max(int(cols["oblique_offs"].numel()) - 1, 0) if have_obl else 0
         n_recent = int(recent.numel()) // 32
-        p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
-        b = _lib.VoteColsBatch(
-            natt=n, n_oblique=p(cols.get("n_oblique")), n_oblique_total=n_oblique_total,
-            bits=cols["attester_bitfield"].data_ptr(), boffs=cols["attester_bitfield_offs"].data_ptr(),
+        p = _lib.dptr
+        b = self._batch(
+            cols, have_obl, natt=n, n_oblique=p(cols.get("n_oblique")), n_oblique_total=n_oblique_total,
             status=p(status), committee=p(committee), parents_start=p(parents_start), take=p(take), recent=p(recent),
-            n_recent=n_recent, members=p(members), coffs=p(coffs), ncomm=max(int(coffs.numel()) - 1, 0), balance=p(balance),
-            **({k: v.data_ptr() for k, v in obl.items()} if have_obl else {}))
+            n_recent=n_recent, members=p(members), coffs=p(coffs), ncomm=max(int(coffs.numel()) - 1, 0), balance=p(balance))
         nbytes = int(lib.dll.pz_vote_cache_scratch_bytes(n, n_recent, n_oblique_total))
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)  # (reused in stream order by the allocator)
-        lib.call("pz_dev_vote_cache_tally", self._h, _lib.ctypes.byref(b), scratch.data_ptr(),
-                 _lib.ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        lib.call("pz_dev_vote_cache_tally", self._h, _lib.ctypes.byref(b), scratch.data_ptr(), _lib.stream_ptr(dev))
 
     def tally_host(self, cols, n, status, committee, parents_start, recent, members, coffs, balance, take=None):
         """The same tally over host arrays (numpy; ``pz_vote_cache_tally``, synchronous)."""
         def arr(a, dt):
             return None if a is None else np.ascontiguousarray(a, dtype=dt)
 
-        keep = {"bits": arr(cols["attester_bitfield"], np.uint8), "boffs": arr(cols["attester_bitfield_offs"], np.uint64),
-                "status": arr(status, np.int32), "committee": arr(committee, np.uint32),
+        keep = {"status": arr(status, np.int32), "committee": arr(committee, np.uint32),
                 "parents_start": arr(parents_start, np.uint64), "take": arr(take, np.uint8),
                 "recent": arr(recent, np.uint8), "members": arr(members, np.uint32), "coffs": arr(coffs, np.uint64),
                 "balance": arr(balance, np.uint64), "n_oblique": arr(cols.get("n_oblique"), np.uint64)}
-        n_oblique_total = 0
-        if all(cols.get(k) is not None for k in _COL_KEYS):
-            keep["oblique_parent_hashes"] = arr(cols["oblique_parent_hashes"], np.uint8)
-            keep["oblique_offs"] = arr(cols["oblique_offs"], np.uint64)
-            keep["oblique_first"] = arr(cols["oblique_first"], np.uint64)
-            n_oblique_total = len(keep["oblique_offs"]) - 1
-        b = _lib.VoteColsBatch(natt=n, n_oblique_total=n_oblique_total, n_recent=keep["recent"].size // 32,
-                               ncomm=len(keep["coffs"]) - 1,
-                               **{k: v.ctypes.data for k, v in keep.items() if v is not None and v.size})
+        have_obl = all(cols.get(k) is not None for k in _COL_KEYS)
+        dtypes = {"attester_bitfield": np.uint8, "oblique_parent_hashes": np.uint8}
+        cols = {k: arr(cols.get(k), dtypes.get(k, np.uint64)) for k in ("attester_bitfield", "attester_bitfield_offs") + _COL_KEYS}
+        b = self._batch(cols, have_obl, natt=n, n_oblique_total=len(cols["oblique_offs"]) - 1 if have_obl else 0,
+                        n_recent=keep["recent"].size // 32, ncomm=len(keep["coffs"]) - 1,
+                        **{k: v.ctypes.data for k, v in keep.items() if v is not None and v.size})
         lib.call("pz_vote_cache_tally", self._h, _lib.ctypes.byref(b))
 
     def read(self, strict=True):
@@ -160,8 +154,7 @@ class DeviceVoteCache:
         totals = np.zeros(k, dtype=np.uint64)
         if k:
             rc = dll.pz_vote_cache_read(self._h, hashes.ctypes.data, totals.ctypes.data, k, _lib.ctypes.byref(cnt))
-        if rc != _lib.PZ_OK and (strict or rc not in (_lib.PZ_EINDEX, _lib.PZ_ERANGE)):
-            raise _lib.PzError(rc, dll.pz_last_error().decode())
+        self._rc(rc, strict)
         return hashes[:cnt.value], totals[:cnt.value]
 
     def items(self, strict=True):
@@ -192,9 +185,8 @@ class DeviceVoteCache:
         n = int(hashes.numel()) // 32
         totals = torch.empty(n, dtype=torch.int64, device=hashes.device)
         slots = torch.empty(n, dtype=torch.int32, device=hashes.device) if want_slots else None
-        p = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
-        lib.call("pz_dev_vote_cache_lookup", self._h, p(hashes), n, p(totals), p(slots),
-                 _lib.ctypes.c_void_p(torch.cuda.current_stream(hashes.device).cuda_stream))
+        p = _lib.dptr
+        lib.call("pz_dev_vote_cache_lookup", self._h, p(hashes), n, p(totals), p(slots), _lib.stream_ptr(hashes.device))
         return totals, slots
 
     def _voters(self, h, strict):
@@ -203,8 +195,7 @@ class DeviceVoteCache:
         key = np.frombuffer(bytes(h), dtype=np.uint8)
         assert key.size == 32
         rc = lib.dll.pz_vote_cache_voters(self._h, key.ctypes.data, words.ctypes.data, _lib.ctypes.byref(present))
-        if rc != _lib.PZ_OK and (strict or rc not in (_lib.PZ_EINDEX, _lib.PZ_ERANGE)):
-            raise _lib.PzError(rc, lib.dll.pz_last_error().decode())
+        self._rc(rc, strict)
         return words, bool(present.value)
 
     def voters(self, h, strict=True):

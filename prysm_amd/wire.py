@@ -240,8 +240,7 @@ def attestations_device(cols, n, field_num=0):
     records are bare, as Attestation.Hash() hashes them."""
     from prysm_amd import _lib
 
-    c = _lib.AttestationCols(*[_lib.ptr(np.ascontiguousarray(cols[k])) if cols.get(k) is not None else None
-                               for k in ATT_COLS])
+    c = _lib.att_cols(cols)
     nbytes = sum(int(cols[k][-1]) for k in ("justified_block_hash_offs", "shard_block_hash_offs",
                                             "attester_bitfield_offs", "oblique_offs")) if n else 0
     ne = int(cols["oblique_first"][-1]) if n else 0
@@ -265,20 +264,24 @@ _BLOCK_DTYPES = {"ts_seconds": np.int64, "ts_nanos": np.int64, "has_timestamp": 
                  "att_block": np.uint32, "status": np.int32}
 
 
+def att_sizes(n, totals):
+    """Entries of every ``ATT_COLS`` column for n rows and the six totals in the header's order
+    (three bytes columns, elements, element bytes, sig values)."""
+    jb, sb, bf, ne, eb, ns = (int(x) for x in totals[:6])
+    size = {k: n + 1 if k.endswith(("_offs", "_first")) else n for k in ATT_COLS}
+    size.update(justified_block_hash=jb, shard_block_hash=sb, attester_bitfield=bf, oblique_parent_hashes=eb,
+                oblique_offs=ne + 1, aggregate_sig=ns)
+    return size
+
+
 def _att_out_sizes(n, nbytes):
     """Entries of every pz_attestation_cols_out column at its bound (include/prysm_hip.h)."""
-    size = {k: n for k in ATT_OUT_COLS}
-    size.update({k: nbytes for k in _BYTES_COLS})
-    size.update({k: n + 1 for k in ATT_COLS if k.endswith("_offs") or k.endswith("_first")})
-    size.update(oblique_offs=nbytes // 2 + 1, aggregate_sig=nbytes)
-    return size
+    return {**{k: n for k in ATT_OUT_COLS}, **att_sizes(n, [nbytes, nbytes, nbytes, nbytes // 2, nbytes, nbytes])}
 
 
 def _att_trim(cols, n, totals):
     """Views of the bound-sized columns at their decoded lengths (``totals`` on the host)."""
-    jb, sb, bf, ne, eb, ns = (int(x) for x in totals[:6])
-    used = dict(justified_block_hash=jb, shard_block_hash=sb, attester_bitfield=bf, oblique_parent_hashes=eb,
-                oblique_offs=ne + 1, aggregate_sig=ns)
+    used = att_sizes(n, totals)
     return {k: v[:used[k]] if k in used else v for k, v in cols.items()}
 
 
@@ -376,7 +379,7 @@ def unwire_attestations_device(d_bytes, d_begs, d_ends, n, field_num=0, nbytes=N
     c = _lib.AttestationColsOut(*[cols[k].data_ptr() for k in ATT_OUT_COLS])
     totals = torch.empty(7, dtype=torch.int64, device=dev)
     scr = torch.empty(int(_lib.lib.dll.pz_unwire_attestations_scratch_bytes(n)), dtype=torch.uint8, device=dev)
-    sh = _lib.ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    sh = _lib.stream_ptr(dev)
     _lib.lib.call("pz_dev_unwire_attestations", d_bytes.data_ptr(), d_begs.data_ptr(), d_ends.data_ptr(), n,
                   field_num, _lib.ctypes.byref(c), totals.data_ptr(), scr.data_ptr(), sh)
     out = {k: v[:size[k]] for k, v in cols.items()}
@@ -401,7 +404,7 @@ def unwire_blocks_device(d_blocks, d_offsets, n, att_cap=None):
     c = _lib.BlockColsOut(*[cols[k].data_ptr() for k in BLOCK_COLS])
     natt = torch.empty(1, dtype=torch.int64, device=dev)
     scr = torch.empty(int(_lib.lib.dll.pz_unwire_blocks_scratch_bytes(n)), dtype=torch.uint8, device=dev)
-    sh = _lib.ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    sh = _lib.stream_ptr(dev)
     _lib.lib.call("pz_dev_unwire_blocks", d_blocks.data_ptr(), d_offsets.data_ptr(), n, cap, _lib.ctypes.byref(c),
                   natt.data_ptr(), scr.data_ptr(), sh)
     out = {k: v[:size[k]] for k, v in cols.items()}
