@@ -105,7 +105,8 @@ int pz_dev_blake2b512_spans(const uint8_t* d_msgs, const uint64_t* d_begs, const
  * load whole aligned chunks, so the buffer must be readable up to the end of the last
  * record's chunk: (n-1)*stride + 128*ceil(len/128) bytes when stride >= 128*ceil(len/128)
  * (the LDS-staged path), (n-1)*stride + 16*ceil(len/16) otherwise; a buffer of n*stride
- * bytes with stride a multiple of 128 always suffices.  Bytes past len never affect a digest. */
+ * bytes with stride a multiple of 128 always suffices; with len == 0 nothing is read.  Bytes
+ * past len never affect a digest. */
 int pz_dev_blake2b512_fixed(const uint8_t* d_msgs, uint64_t stride, uint64_t len, uint64_t n,
                             uint8_t* d_out, uint32_t out_bytes, void* stream);
 

@@ -67,10 +67,13 @@ pz_b2b_fixed_kernel(const uint8_t* __restrict__ msgs, uint64_t stride, uint64_t 
     // ---- stage: 512 16-byte chunks (64 msgs x 8 parts), 8 per lane, all loads in flight
     const uint32_t boff = (uint32_t)t * 128u + lpart * 16u;
     uint4 v[8];
-    if (full_wave && (t + 1 < nblocks || (len & 127) == 0)) {  // wave-uniform fast path
+    if (full_wave && (t + 1 < nblocks || (len != 0 && (len & 127) == 0))) {  // wave-uniform fast path
 #pragma unroll
       for (int it = 0; it < 8; ++it)
         v[it] = *reinterpret_cast<const uint4*>(wbase + ((it * 8u + lrow) * s32 + boff));
+    } else if (len == 0) {  // wave-uniform: the empty message's one all-zero block; nothing is read
+#pragma unroll
+      for (int it = 0; it < 8; ++it) v[it] = make_uint4(0, 0, 0, 0);
     } else {  // tail wave / partial last block: clamp addresses, zero what lies outside
       const uint32_t safe_off = boff < (uint32_t)len ? boff : 0u;
 #pragma unroll
@@ -131,10 +134,6 @@ struct FixedGeom {
 
 __device__ __forceinline__ uint32_t chunk_pos(uint32_t r, uint32_t k) { return k ^ ((r >> 1) & 7u); }
 
-__device__ __forceinline__ bool block_is_full(const FixedGeom& G, uint64_t g, uint64_t t) {
-  return g * 64 + 64 <= G.n && (t + 1 < G.nblocks || (G.len & 127) == 0);
-}
-
 // Full block: 8 DMA instructions.  Instruction `it`, lane L fills row r = it*8 + L/8 at
 // position p = L%8, i.e. global chunk k = p ^ ((r>>1)&7) (the swizzle is an involution).
 __device__ __forceinline__ void dma_block(uint8_t* slab, const FixedGeom& G, uint64_t g, uint64_t t) {
@@ -145,32 +144,6 @@ __device__ __forceinline__ void dma_block(uint8_t* slab, const FixedGeom& G, uin
     const uint32_t k = chunk_pos(r, G.lpart);
     const uint8_t* src = wbase + (r * G.s32 + (uint32_t)t * 128u + k * 16u);
     __builtin_amdgcn_global_load_lds((gbl_void_t*)src, (lds_void_t*)(slab + it * 1024), 16, 0, 0);
-  }
-}
-
-// Tail wave / partial last block: register path with clamped addresses and zero masking,
-// written into the same swizzled layout.
-__device__ __forceinline__ void reg_block(uint8_t* slab, const FixedGeom& G, uint64_t g, uint64_t t) {
-  const uint64_t m0 = g * 64;
-  const uint8_t* wbase = G.msgs + m0 * G.stride;
-  const uint32_t rows_left = m0 + 64 <= G.n ? 64u : (uint32_t)(G.n - m0);
-  const uint32_t len = (uint32_t)G.len;
-  const uint32_t boff = (uint32_t)t * 128u + G.lpart * 16u;
-  const uint32_t safe_off = boff < len ? boff : 0u;
-  uint4 v[8];
-#pragma unroll
-  for (int it = 0; it < 8; ++it) {
-    const uint32_t r = it * 8u + G.lrow;
-    const bool ok = r < rows_left && boff < len;
-    const uint32_t rr = r < rows_left ? r : 0u;
-    uint4 q = *reinterpret_cast<const uint4*>(wbase + (rr * G.s32 + safe_off));
-    if (boff + 16 > len) q = mask_chunk(q, boff < len ? len - boff : 0u);
-    v[it] = ok ? q : make_uint4(0, 0, 0, 0);
-  }
-#pragma unroll
-  for (int it = 0; it < 8; ++it) {
-    const uint32_t r = it * 8u + G.lrow;
-    *reinterpret_cast<uint4*>(slab + r * 128u + chunk_pos(r, G.lpart) * 16u) = v[it];
   }
 }
 
@@ -436,8 +409,9 @@ hipError_t launch_b2b_fixed(const uint8_t* msgs, uint64_t stride, uint64_t len, 
   if (n == 0) return hipSuccess;
   const uint64_t nblocks = len == 0 ? 1 : (len + 127) / 128;
   const uint64_t nfull = n & ~63ull;
-  // (strided inputs narrower than whole blocks, and under one full wave: the plain grid)
-  if (stride < nblocks * 128 || nfull == 0)
+  // (strided inputs narrower than whole blocks, under one full wave, and empty messages, of
+  // which the plain grid reads nothing while the DMA would fetch a block per record: the plain grid)
+  if (stride < nblocks * 128 || nfull == 0 || len == 0)
     return launch_plain(msgs, stride, len, n, out, out_bytes, stream);
   // persistent grid: 4 resident 256-thread workgroups per CU (122 VGPRs -> 4 waves/SIMD)
   const uint64_t groups = nfull / 64;

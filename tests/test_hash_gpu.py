@@ -136,3 +136,50 @@ def test_batch_api_thread_safe():
     assert not errs, errs
     for msgs, got in zip(batches, out):
         assert got == [ref.sum512(m) for m in msgs]
+
+
+def _batch_from(msgs, lead, out_bytes, null_msgs=False):
+    """pz_blake2b512_batch over ``msgs`` packed behind ``lead`` poison bytes: offsets[0] == lead."""
+    n = len(msgs)
+    offsets = np.full(n + 1, lead, dtype=np.uint64)
+    offsets[1:] += np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+    data = np.frombuffer(b"\xEE" * lead + b"".join(msgs) + b"\xEE" * 16, dtype=np.uint8)
+    out = np.full((n, out_bytes), 0xA5, dtype=np.uint8)
+    _lib.lib.call("pz_blake2b512_batch", None if null_msgs else data.ctypes.data, offsets.ctypes.data, n,
+                  out.ctypes.data, out_bytes)
+    return [bytes(r) for r in out]
+
+
+def test_nonzero_first_offset_on_every_route():
+    """hash_batch_on rebases by offsets[0] on each of its routes (pz_comm_blake2b512_batch relies on
+    it for every rank but the first): five poison bytes in front of the first message, on the
+    small-batch host route, the CSR route, the uniform route and the long-message route."""
+    rng = np.random.default_rng(31)
+
+    def rand(lens):
+        return [rng.integers(0, 256, size=int(l), dtype=np.uint8).tobytes() for l in lens]
+
+    short = rand([3, 130, 64])
+    ragged = rand(rng.integers(0, 700, size=200))
+    uniform = rand([144] * 300)
+    mixed = rand([0, 999, 1000, 1001, 5, 70000, 128, 1000, 3])
+    for ob in (32, 64):
+        with _lib.small_batch_threshold(_lib.SMALL_BATCH_DEFAULT):
+            assert _batch_from(short, 5, ob) == [ref.sum512(m)[:ob] for m in short]
+        assert _batch_from(short, 5, ob) == [ref.sum512(m)[:ob] for m in short]  # the same on the GPU
+        assert _batch_from(ragged, 5, ob) == [ref.sum512(m)[:ob] for m in ragged]
+        assert _batch_from(uniform, 5, ob) == [ref.sum512(m)[:ob] for m in uniform]
+        with _lib.serial_threshold(1000):
+            assert _batch_from(mixed, 5, ob) == [ref.sum512(m)[:ob] for m in mixed]
+
+
+@pytest.mark.parametrize("null_msgs", [True, False])
+@pytest.mark.parametrize("n", [1, 64, 300])
+def test_only_empty_messages(n, null_msgs):
+    """A batch of nothing but empty messages, which check_batch_args allows with msgs == NULL, on the
+    GPU route and on the small-batch host route, at offsets[0] 0 and 5."""
+    for thr in (0, _lib.SMALL_BATCH_DEFAULT):
+        with _lib.small_batch_threshold(thr):
+            for lead in (0, 5):
+                for ob in (32, 64):
+                    assert _batch_from([b""] * n, lead, ob, null_msgs) == [ref.sum512(b"")[:ob]] * n
