@@ -138,7 +138,10 @@ uint64_t pz_wire_scratch_bytes(uint64_t n);
 int pz_wire_validators(const pz_validator_cols* v, uint64_t n, uint32_t field_num, uint8_t* out,
                        uint64_t cap, uint64_t* offsets, uint64_t* len);
 /* Device pointers (columns included), caller's stream.  d_out must hold
- * pz_wire_validators_bound(...) bytes; *d_total (device) receives the length. */
+ * pz_wire_validators_bound(...) bytes; *d_total (device) receives the length.  Nothing outside
+ * d_out[0, *d_total) is written: not the rest of the bound, not a byte before d_out, whatever
+ * d_out's alignment; with n == 0 d_out is not touched and may be NULL.  d_scratch need not be
+ * cleared: every call resets what it uses. */
 int pz_dev_wire_validators(const pz_validator_cols* v, uint64_t n, uint32_t field_num, uint8_t* d_out,
                            uint64_t* d_offsets, void* d_scratch, uint64_t* d_total, void* stream);
 
@@ -175,7 +178,9 @@ uint64_t pz_wire_attestations_scratch_bytes(uint64_t n);
 int pz_wire_attestations(const pz_attestation_cols* a, uint64_t n, uint32_t field_num, uint8_t* out,
                          uint64_t cap, uint64_t* offsets, uint64_t* len);
 /* Device pointers, caller's stream; d_out holds pz_wire_attestations_bound(...) bytes,
- * d_offsets n+1 entries (required). */
+ * d_offsets n+1 entries (required).  Nothing outside d_out[0, d_offsets[n]) is written: not the
+ * rest of the bound, not a byte before d_out, whatever d_out's alignment.  Ranges need not start
+ * at 0 here; d_scratch need not be cleared: every call resets what it uses. */
 int pz_dev_wire_attestations(const pz_attestation_cols* a, uint64_t n, uint32_t field_num, uint8_t* d_out,
                              uint64_t* d_offsets, void* d_scratch, void* stream);
 
