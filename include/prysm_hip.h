@@ -997,6 +997,115 @@ uint64_t pz_state_recalc_scratch_bytes(uint64_t nval, uint64_t rows_cap, uint32_
 int pz_dev_state_recalc(pz_recalc_state* st, pz_att_pool* pool, pz_vote_cache* cache /* NULL: no entry */,
                         const pz_recalc_batch* b, void* d_scratch, void* stream);
 
+/* ---- a2 / R: the two states' proto3 bytes and roots from the resident objects -----------------------
+ * What PersistActiveState / PersistCrystallizedState store (blockchain/core.go:161-177, proto.Marshal
+ * at types/state.go:141, 240) and what ActiveState.Hash() / CrystallizedState.Hash() hash
+ * (types/state.go:138-149, 237-248), from pz_att_pool, pz_recalc_state and the caller's validator
+ * columns where they lie.  In the kernels these entry points add (wire_state.hip) no workgroup waits
+ * for another; pz_dev_wire_validators and pz_dev_wire_attestations run inside them as they are.
+ *
+ * ShardAndCommitteesForSlots (CrystallizedState field 12, messages.proto:72, 75-77, 87-90; replaces
+ * that span of proto.Marshal at types/state.go:240) from the committee table in pz_att_check_batch's
+ * form plus the committees' members (pz_recalc_batch's CSR): array a holds entries arr_offs[a] ..
+ * arr_offs[a+1]; entry e has shard arr_shard[e] and the members of committee arr_comm[e] (entries
+ * may share a committee).  Per array: the key of field_num, the length, then per entry 0a, length,
+ * shard_id (field 1, absent when 0) and committee (packed field 2, absent when empty).  field_num
+ * follows pz_wire_validators' rule (0: the arrays' bare bodies). */
+typedef struct pz_committee_table {
+  uint64_t narr;                   /* len(ShardAndCommitteesForSlots) */
+  const uint64_t* arr_offs;        /* narr+1, arr_offs[0] == 0 */
+  const uint64_t* arr_shard;       /* entry -> ShardId */
+  const uint32_t* arr_comm;        /* entry -> committee id */
+  uint64_t ncomm;
+  const uint64_t* coffs;           /* ncomm+1 */
+  const uint32_t* members;         /* committee c = members[coffs[c] .. coffs[c+1]) */
+} pz_committee_table;
+/* Upper bound of the encoded length (types/state.go:240's span; sizes d_out). */
+uint64_t pz_wire_committees_bound(uint64_t narr, uint64_t nentries, uint64_t members_cap);
+/* Device scratch the pz_dev_ form needs (no reference counterpart). */
+uint64_t pz_wire_committees_scratch_bytes(uint64_t narr, uint64_t nentries, uint64_t members_cap);
+/* Device pointers, caller's stream, four dependent launches (plan, size, scan, write: DESIGN.md §3).
+ * nentries and members_cap (an upper bound of the sum of the entries' committee sizes) are host
+ * values that size the launches and the scratch; the true sums are read on the device.
+ * d_result[0] receives the length and d_result[1] the status: PZ_ERANGE when arr_offs[0] != 0,
+ * arr_offs decreases, arr_offs[narr] != nentries, a committee's range is inverted or the member sum
+ * exceeds members_cap; PZ_EINDEX when an arr_comm[e] >= ncomm.  With a status nothing of d_out is
+ * written, the length is 0 and the call still returns PZ_OK.  Nothing outside d_out[0, length) is
+ * written, whatever d_out's alignment; narr == 0 gives length 0 and d_out may be NULL.  d_scratch
+ * need not be cleared.  PZ_EINVAL, before any launch: a NULL t, d_result, or (narr > 0) d_out,
+ * arr_offs, (nentries > 0) entry columns or coffs, (members_cap > 0) members; d_scratch NULL or not
+ * 16-byte aligned; 2^31 arrays or entries, 2^40 members, or field_num >= 2^29; a table the write
+ * launch's grid cannot cover: members_cap / 256 + nentries + ceil((nentries + narr) / 256) must stay
+ * below 2^31.  The plan and scan launches are one workgroup each, serial over the entries in steps
+ * of 1,024. */
+int pz_dev_wire_committees(const pz_committee_table* t, uint64_t nentries, uint64_t members_cap, uint32_t field_num,
+                           uint8_t* d_out, uint64_t* d_result /* [2]: length, status */, void* d_scratch, void* stream);
+/* Host pointers, synchronous (types/state.go:240's span).  The table's status is the return value;
+ * PZ_ERANGE also when the encoding exceeds cap (*len still receives its length, nothing written). */
+int pz_wire_committees(const pz_committee_table* t, uint64_t nentries, uint32_t field_num, uint8_t* out, uint64_t cap,
+                       uint64_t* len);
+
+/* The stored CrystallizedState (messages.proto:59-72; proto.Marshal at types/state.go:240) from a
+ * pz_recalc_state: fields 1-5 and 7 are the handle's scalars, field 10 its crosslink records
+ * (messages.proto:122-126; zero scalars and an empty hash absent, so a record of three zero fields
+ * is 52 00), field 11 pz_dev_wire_validators over v, field 12 the caller's already encoded span
+ * (pz_dev_wire_committees; the table changes only at a dynasty transition, core.go:470), and the
+ * fields the handle does not hold come by value: */
+typedef struct pz_cstate_rest {
+  uint64_t crosslinking_start_shard;       /* field 6 */
+  uint8_t  dynasty_seed[64];               /* field 8 */
+  uint32_t dynasty_seed_len;               /* PZ_EINVAL above 64 */
+  uint64_t dynasty_seed_last_reset;        /* field 9 */
+} pz_cstate_rest;
+/* Bytes d_out must hold (val_bytes_total: both bytes columns' total length); types/state.go:240. */
+uint64_t pz_crystallized_state_bound(uint32_t nrec, uint32_t hash_stride, uint64_t nval, uint64_t val_bytes_total,
+                                     uint64_t field12_len);
+/* Device scratch of the pz_dev_ form (no reference counterpart). */
+uint64_t pz_crystallized_state_scratch_bytes(uint64_t nval);
+/* proto.Marshal(CrystallizedState), types/state.go:240, on the caller's stream with no wait: the
+ * head (fields 1-10) is written right-aligned so that it ends at the host-known head bound H, the
+ * validators start at d_out + H, and a tail launch that reads their length on the device copies
+ * d_field12 behind them.  The message is d_out[d_span[0], d_span[0] + d_span[1]); nothing outside
+ * it is written.  v and d_field12 are device pointers.  PZ_EINVAL, before any launch: a NULL st,
+ * rest, v, d_out or d_span, field12_len > 0 with a NULL d_field12, a seed above 64 bytes, d_scratch
+ * NULL or not 16-byte aligned. */
+int pz_dev_crystallized_state_bytes(pz_recalc_state* st, const pz_cstate_rest* rest, const pz_validator_cols* v, uint64_t nval,
+                                    const uint8_t* d_field12, uint64_t field12_len, uint8_t* d_out,
+                                    uint64_t* d_span /* [2]: begin, length */, void* d_scratch, void* stream);
+/* PersistCrystallizedState's bytes (core.go:170-177) and, with root, CrystallizedState.Hash()
+ * (types/state.go:237-248): allocates what it needs, waits for the handle's last call and for its
+ * own, copies the message to out (host) and hashes it on the host route of long messages.
+ * PZ_ERANGE, *len set, out untouched, when the message exceeds cap.  The handle's sticky PZ_EINDEX
+ * comes as pz_recalc_state_read reports it: the outputs are filled all the same and hold the state
+ * before the panicking call.  The call runs on the library's own stream and orders itself against
+ * st's earlier calls only: what produces v's columns and d_field12 (pz_dev_wire_committees makes no
+ * wait) must have completed before it, the caller synchronising those streams first. */
+int pz_crystallized_state_read(pz_recalc_state* st, const pz_cstate_rest* rest, const pz_validator_cols* v /* device */,
+                               uint64_t nval, const uint8_t* d_field12, uint64_t field12_len, uint8_t* out /* host */,
+                               uint64_t cap, uint64_t* len, uint8_t root[32] /* optional */);
+
+/* The stored ActiveState (messages.proto:94-97; proto.Marshal at types/state.go:141) from a
+ * pz_att_pool: field 1 is pz_dev_wire_attestations over pz_att_pool_view, field 2
+ * (recent_block_hashes) one lane per hash, written at the device-known end of field 1: entry i is
+ * 12, its length and the LAST recent_len[i] bytes of row i (common.BytesToHash right-aligns; the
+ * genesis state's 128 empty entries, types/state.go:46-57, are 12 00 each).
+ * The bound for the pool's seven counts (types/state.go:141; sizes d_out): */
+uint64_t pz_active_state_bound(const uint64_t counts[7], uint64_t n_recent);
+/* proto.Marshal(ActiveState), types/state.go:141, on the caller's stream.  The call makes ONE wait,
+ * for the pool's seven counts (pz_dev_wire_attestations takes its row count from the host), as
+ * pz_dev_state_recalc does.  *d_total (device) receives the length; nothing outside
+ * d_out[0, *d_total) is written.  PZ_ERANGE, nothing written, when cap is below
+ * pz_active_state_bound of those counts.  The pool's sticky error is returned as
+ * pz_att_pool_counts returns it, the output written all the same.  d_recent: n_recent x 32 bytes,
+ * BytesToHash-normalised; d_recent_len optional (NULL: all 32; values above 32 count as 32). */
+int pz_dev_active_state_bytes(pz_att_pool* pool, const uint8_t* d_recent, const uint8_t* d_recent_len, uint64_t n_recent,
+                              uint8_t* d_out, uint64_t cap, uint64_t* d_total, void* stream);
+/* PersistActiveState's bytes (core.go:161-168) and, with root, ActiveState.Hash()
+ * (types/state.go:138-149), over host recent / recent_len; waits for the pool's last call.
+ * PZ_ERANGE, *len set, out untouched, when the message exceeds cap. */
+int pz_active_state_read(pz_att_pool* pool, const uint8_t* recent, const uint8_t* recent_len, uint64_t n_recent,
+                         uint8_t* out, uint64_t cap, uint64_t* len, uint8_t root[32] /* optional */);
+
 typedef struct pz_block_result {
   uint8_t hash[32];      /* Block.Hash() */
   int32_t status;        /* PZ_BLOCK_* */

@@ -132,6 +132,17 @@ SIGNATURES = {
     "pz_recalc_state_read": [vp, vp, vp, vp, vp, vp, vp],
     "pz_state_recalc_scratch_bytes": [u64, u64, u32],
     "pz_dev_state_recalc": [vp, vp, vp, vp, vp, vp],
+    "pz_wire_committees_bound": [u64, u64, u64],
+    "pz_wire_committees_scratch_bytes": [u64, u64, u64],
+    "pz_dev_wire_committees": [vp, u64, u64, u32, vp, vp, vp, vp],
+    "pz_wire_committees": [vp, u64, u32, vp, u64, c_u64p],
+    "pz_crystallized_state_bound": [u32, u32, u64, u64, u64],
+    "pz_crystallized_state_scratch_bytes": [u64],
+    "pz_dev_crystallized_state_bytes": [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp],
+    "pz_crystallized_state_read": [vp, vp, vp, u64, vp, u64, vp, u64, c_u64p, vp],
+    "pz_active_state_bound": [vp, u64],
+    "pz_dev_active_state_bytes": [vp, vp, vp, u64, vp, u64, vp, vp],
+    "pz_active_state_read": [vp, vp, vp, u64, vp, u64, c_u64p, vp],
     "pz_shutdown": [],
     "pz_state_new": [u64, ctypes.c_int, vp],
     "pz_state_upload": [vp, vp, vp, vp],
@@ -285,6 +296,18 @@ class RecalcBatch(ctypes.Structure):
     ]
 
 
+class CommitteeTable(ctypes.Structure):
+    """Mirror of ``pz_committee_table`` (include/prysm_hip.h)."""
+    _fields_ = [("narr", u64), ("arr_offs", vp), ("arr_shard", vp), ("arr_comm", vp), ("ncomm", u64), ("coffs", vp),
+                ("members", vp)]
+
+
+class CstateRest(ctypes.Structure):
+    """Mirror of ``pz_cstate_rest`` (include/prysm_hip.h)."""
+    _fields_ = [("crosslinking_start_shard", u64), ("dynasty_seed", ctypes.c_uint8 * 64), ("dynasty_seed_len", u32),
+                ("dynasty_seed_last_reset", u64)]
+
+
 RS_LAST_STATE_RECALC, RS_JUSTIFIED_STREAK, RS_LAST_JUSTIFIED_SLOT, RS_LAST_FINALIZED_SLOT, RS_CURRENT_DYNASTY, \
     RS_TOTAL_DEPOSITS = range(6)  # pz_recalc_state's scalars
 RS_COUNT = 8
@@ -298,7 +321,9 @@ _RESTYPES = {"pz_last_error": ctypes.c_char_p, "pz_chain_free": None, "pz_set_se
              "pz_unwire_attestations_scratch_bytes": u64, "pz_unwire_blocks_scratch_bytes": u64,
              "pz_vote_cache_free": None, "pz_vote_cache_scratch_bytes": u64,
              "pz_att_pool_free": None, "pz_att_pool_scratch_bytes": u64,
-             "pz_recalc_state_free": None, "pz_state_recalc_scratch_bytes": u64}
+             "pz_recalc_state_free": None, "pz_state_recalc_scratch_bytes": u64,
+             "pz_wire_committees_bound": u64, "pz_wire_committees_scratch_bytes": u64,
+             "pz_crystallized_state_bound": u64, "pz_crystallized_state_scratch_bytes": u64, "pz_active_state_bound": u64}
 SERIAL_DEFAULT = 65536        # the library's default serial threshold (bytes)
 SERIAL_ON_GPU = (1 << 64) - 1  # pz_set_serial_threshold value that keeps every message on the GPU
 

@@ -501,6 +501,18 @@ def state_recalc_resident(pool, cache, state, recent_hashes, block_slot):
         raise
 
 
+def resident_state_roots(pool, state, recent_hashes, field12, recent_len=None, crosslinking_start_shard=0, dynasty_seed=b"",
+                         dynasty_seed_last_reset=0):
+    """``(ActiveState.Hash(), CrystallizedState.Hash())`` (types/state.go:138-149, 237-248) -- the two
+    digests a proposer writes into a block -- of the states held in ``pool`` (a
+    ``prysm_amd.pending.DevicePendingAttestations``) and ``state`` (a
+    ``prysm_amd.pending.ResidentRecalcState``), encoded on the device where they lie.
+    ``recent_hashes`` / ``recent_len``: as ``DevicePendingAttestations.active_state``; ``field12`` and
+    the remaining arguments: as ``ResidentRecalcState.wire``."""
+    return (pool.active_state_root(recent_hashes, recent_len),
+            state.root(field12, crosslinking_start_shard, dynasty_seed, dynasty_seed_last_reset))
+
+
 def serialize_blocks(blocks):
     """pb.BeaconBlock list -> (uint8 data, uint64 offsets[n+1]) of canonical encodings."""
     enc = [wire.beacon_block(b) for b in blocks]

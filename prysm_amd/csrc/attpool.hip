@@ -363,6 +363,8 @@ int att_pool_peek(pz_att_pool* h, ApView* v, hipStream_t s) {
   return PZ_OK;
 }
 
+Resident* resident_of(pz_att_pool* h) { return h; }
+
 void att_pool_note_rows(pz_att_pool* h, uint64_t rows) {
   std::lock_guard<std::mutex> lk(h->mu);
   h->rows_ub = rows;

@@ -304,6 +304,23 @@ int enqueue(pz_recalc_state* h, pz_att_pool* pool, pz_vote_cache* cache, const p
 }
 
 }  // namespace
+
+Resident* resident_of(pz_recalc_state* h) { return h; }
+
+int recalc_state_view(pz_recalc_state* h, RsView* v, hipStream_t s, bool record) {
+  if (!h || !v) return fail(PZ_EINVAL, "recalc state is null");
+  std::lock_guard<std::mutex> lk(h->mu);
+  v->device = h->device;
+  v->nrec = h->nrec, v->stride = h->stride;
+  v->words = static_cast<const uint64_t*>(h->words.ptr);
+  v->rec_dynasty = static_cast<const uint64_t*>(h->rec_dynasty.ptr);
+  v->rec_slot = static_cast<const uint64_t*>(h->rec_slot.ptr);
+  v->rec_hash = static_cast<const uint8_t*>(h->rec_hash.ptr);
+  v->rec_hash_len = static_cast<const uint32_t*>(h->rec_hash_len.ptr);
+  if (record) h->last = s;
+  return PZ_OK;
+}
+
 }  // namespace pz
 
 using namespace pz;

@@ -63,6 +63,11 @@ struct HostForm {
   }
 };
 
+// A handle as its Resident base, for a host-pointer form written outside the handle's own file
+// (wire_state.hip); defined beside each struct.
+Resident* resident_of(pz_att_pool* h);
+Resident* resident_of(pz_recalc_state* h);
+
 // The vote cache's lookup side: device pointers, valid for the handle's lifetime.
 struct VcView {
   int device;
@@ -89,5 +94,19 @@ struct ApView {
 int att_pool_peek(pz_att_pool* h, ApView* v, hipStream_t s);
 // The exact row count the host has just read: the next prune's grid.
 void att_pool_note_rows(pz_att_pool* h, uint64_t rows);
+
+// The recalc state's words (scalars[PZ_RS_COUNT], then the sticky error word) and record columns,
+// valid for the handle's lifetime.
+struct RsView {
+  int device;
+  uint32_t nrec, stride;
+  const uint64_t* words;
+  const uint64_t* rec_dynasty;
+  const uint64_t* rec_slot;
+  const uint8_t* rec_hash;
+  const uint32_t* rec_hash_len;
+};
+// Fills *v; with record, s becomes the stream the handle's reads wait for (wire_state.hip).
+int recalc_state_view(pz_recalc_state* h, RsView* v, hipStream_t s, bool record);
 
 }  // namespace pz

@@ -170,6 +170,35 @@ class DevicePendingAttestations(_lib.Handle):
         offs = offs.cpu().numpy().view(np.uint64)
         return out[:int(offs[-1])].cpu().numpy().tobytes(), offs
 
+    def _stored(self, recent, recent_len, want_root, strict):
+        from prysm_amd.blockchain import _recent_array
+
+        rows = _recent_array(recent)
+        n = len(rows)
+        lens = None if recent_len is None else np.ascontiguousarray(recent_len, dtype=np.uint8)
+        assert lens is None or lens.shape == (n,)
+        counts = self.counts(strict=False)
+        cap = int(lib.dll.pz_active_state_bound(counts.ctypes.data, n))
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        length = _lib.ctypes.c_uint64(0)
+        root = np.zeros(32, dtype=np.uint8)
+        rc = lib.dll.pz_active_state_read(self._h, _lib.ptr(rows), _lib.ptr(lens), n, out.ctypes.data, cap,
+                                          _lib.ctypes.byref(length), root.ctypes.data if want_root else None)
+        self._rc(rc, strict)
+        return out[:length.value].tobytes(), root.tobytes()
+
+    def active_state(self, recent, recent_len=None, strict=True):
+        """The stored ActiveState (PersistActiveState, blockchain/core.go:161-168) encoded on the
+        device: the pool as field 1, then ``recent`` = RecentBlockHashes() (byte strings, normalised
+        here, or a (k, 32) uint8 array) as field 2, entry i being the last ``recent_len[i]`` bytes of
+        its row (None: all 32; the genesis state's entries are empty: all 0).
+        ``pz_active_state_read``."""
+        return self._stored(recent, recent_len, False, strict)[0]
+
+    def active_state_root(self, recent, recent_len=None, strict=True):
+        """ActiveState.Hash() (types/state.go:138-149) of :meth:`active_state`'s message, 32 bytes."""
+        return self._stored(recent, recent_len, True, strict)[1]
+
     def shard_block_hashes(self, rows):
         """ShardBlockHash of the named rows, a list of byte strings: what a crosslink winner writes
         into its record (core.go:550-554)."""
@@ -297,6 +326,58 @@ class ResidentRecalcState(_DeviceValidators, _lib.Handle):
     def winners(self, strict=True):
         """The last call's winners: one pool row (before the prune) per record, 0xFFFFFFFF: none."""
         return self.read(strict)["winner"]
+
+    def _field12(self, field12):
+        """Field 12 as a uint8 device tensor: bytes are uploaded; the ``(out, result)`` pair of
+        ``wire.committees_device`` is cut at its length (a table error raises)."""
+        import torch
+
+        dev = self.balance.device
+        if isinstance(field12, tuple):
+            out, result = field12
+            length, status = (int(x) for x in result.cpu())
+            if status != _lib.PZ_OK:
+                raise _lib.PzError(status, "the committee table was refused")
+            return out[:length]
+        if hasattr(field12, "data_ptr"):
+            return field12
+        raw = np.frombuffer(bytes(field12), dtype=np.uint8)
+        return torch.from_numpy(raw.copy()).to(dev) if raw.size else torch.empty(0, dtype=torch.uint8, device=dev)
+
+    def validator_cols(self):
+        """``pz_validator_cols`` over the resident balance / start / end (the other fields zero)."""
+        return _lib.ValidatorCols(balance=self.balance.data_ptr(), start_dynasty=self.start.data_ptr(),
+                                  end_dynasty=self.end.data_ptr())
+
+    def _stored(self, field12, crosslinking_start_shard, dynasty_seed, dynasty_seed_last_reset, want_root, strict):
+        f12 = self._field12(field12)
+        seed = bytes(dynasty_seed)
+        rest = _lib.CstateRest(crosslinking_start_shard=int(crosslinking_start_shard), dynasty_seed_len=len(seed),
+                               dynasty_seed_last_reset=int(dynasty_seed_last_reset))
+        if len(seed) <= 64:
+            _lib.ctypes.memmove(rest.dynasty_seed, seed, len(seed))
+        cols = self.validator_cols()
+        cap = int(lib.dll.pz_crystallized_state_bound(self.nrec, self.hash_stride, self.nval, 0, int(f12.numel())))
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        length = _lib.ctypes.c_uint64(0)
+        root = np.zeros(32, dtype=np.uint8)
+        rc = lib.dll.pz_crystallized_state_read(self._h, _lib.ctypes.byref(rest), _lib.ctypes.byref(cols), self.nval,
+                                                _lib.dptr(f12), int(f12.numel()), out.ctypes.data, cap,
+                                                _lib.ctypes.byref(length), root.ctypes.data if want_root else None)
+        self._rc(rc, strict)
+        return out[:length.value].tobytes(), root.tobytes()
+
+    def wire(self, field12, crosslinking_start_shard=0, dynasty_seed=b"", dynasty_seed_last_reset=0, strict=True):
+        """The stored CrystallizedState (PersistCrystallizedState, blockchain/core.go:170-177) encoded
+        on the device from the handle, the resident validators and ``field12`` -- the already encoded
+        ShardAndCommitteesForSlots: bytes, a uint8 device tensor, or what ``wire.committees_device``
+        returns for device columns (``pz_crystallized_state_read``).  The remaining arguments are the
+        fields the handle does not hold."""
+        return self._stored(field12, crosslinking_start_shard, dynasty_seed, dynasty_seed_last_reset, False, strict)[0]
+
+    def root(self, field12, crosslinking_start_shard=0, dynasty_seed=b"", dynasty_seed_last_reset=0, strict=True):
+        """CrystallizedState.Hash() (types/state.go:237-248) of :meth:`wire`'s message, 32 bytes."""
+        return self._stored(field12, crosslinking_start_shard, dynasty_seed, dynasty_seed_last_reset, True, strict)[1]
 
 
 for _i, _name in enumerate(ResidentRecalcState._SCALARS):

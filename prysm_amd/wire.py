@@ -412,3 +412,76 @@ def unwire_blocks_device(d_blocks, d_offsets, n, att_cap=None):
     out["bytes_len"] = out["bytes_len"].view(n, 5)
     out["natt"] = natt
     return out
+
+
+# ---- ShardAndCommitteesForSlots on the device (prysm_amd/csrc/wire_state.hip) ------------------
+TABLE_COLS = ("arr_offs", "arr_shard", "arr_comm", "coffs", "members")
+
+
+def committee_table(shard_and_committees):
+    """ShardAndCommitteesForSlots -- a list (one per slot) of lists of ``(shard_id, committee)``
+    pairs, or of ``pb.ShardAndCommitteeArray`` -- as the columns of ``pz_committee_table``: one
+    committee per entry."""
+    arrays = [[(sc.shard_id, sc.committee) for sc in a.array_shard_and_committee]
+              if hasattr(a, "array_shard_and_committee") else list(a) for a in shard_and_committees]
+    entries = [e for arr in arrays for e in arr]
+    arr_offs = np.zeros(len(arrays) + 1, dtype=_U64)
+    arr_offs[1:] = np.cumsum([len(arr) for arr in arrays], dtype=_U64)
+    coffs = np.zeros(len(entries) + 1, dtype=_U64)
+    coffs[1:] = np.cumsum([len(e[1]) for e in entries], dtype=_U64)
+    members = np.concatenate([np.asarray(e[1], dtype=np.uint32) for e in entries] + [np.zeros(0, np.uint32)])
+    return {"arr_offs": arr_offs, "arr_shard": np.array([e[0] & M64 for e in entries], dtype=_U64),
+            "arr_comm": np.arange(len(entries), dtype=np.uint32), "coffs": coffs,
+            "members": np.ascontiguousarray(members, dtype=np.uint32)}
+
+
+def _table_struct(table, address):
+    from prysm_amd import _lib
+
+    t = _lib.CommitteeTable(narr=len(table["arr_offs"]) - 1, ncomm=len(table["coffs"]) - 1)
+    for k in TABLE_COLS:
+        setattr(t, k, address(table[k]))
+    return t
+
+
+def committees_device(table, field_num=12, members_cap=None):
+    """ShardAndCommitteesForSlots encoded on the GPU, each array framed as repeated message
+    ``field_num`` (CrystallizedState.shard_and_committees_for_slots = 12): the bytes
+    :func:`crystallized_state` emits for that field.
+
+    ``table``: ShardAndCommitteesForSlots itself (see :func:`committee_table`) or the table's
+    columns as a dict keyed as ``TABLE_COLS``.  Host columns (numpy) go through
+    ``pz_wire_committees`` and the result is ``bytes``.  Device columns (torch; int64 / int32
+    carrying the unsigned values) go through ``pz_dev_wire_committees`` on the current stream: the
+    result is ``(out, result)``, a uint8 tensor at its bound and an int64 tensor ``[length, status]``.
+    ``members_cap`` bounds the sum of the entries' committee sizes (None: the number of members,
+    right when no two entries share a committee); the call makes no wait."""
+    from prysm_amd import _lib
+
+    if not isinstance(table, dict):
+        table = committee_table(table)
+    nentries = len(table["arr_comm"])
+    if not hasattr(table["arr_offs"], "data_ptr"):
+        table = {k: np.ascontiguousarray(table[k]) for k in TABLE_COLS}
+        t = _table_struct(table, _lib.ptr)
+        coffs, comm = table["coffs"], table["arr_comm"].astype(np.int64)
+        ok = comm[comm < len(coffs) - 1]
+        cap = int(_lib.lib.dll.pz_wire_committees_bound(t.narr, nentries, int((coffs[ok + 1] - coffs[ok]).sum())))
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        length = _lib.ctypes.c_uint64(0)
+        _lib.lib.call("pz_wire_committees", _lib.ctypes.byref(t), nentries, field_num, _lib.ptr(out), cap,
+                      _lib.ctypes.byref(length))
+        return out[:length.value].tobytes()
+    import torch
+
+    dev = table["arr_offs"].device
+    t = _table_struct(table, _lib.dptr)
+    members_cap = int(table["members"].numel()) if members_cap is None else int(members_cap)
+    dll = _lib.lib.dll
+    out = torch.empty(max(int(dll.pz_wire_committees_bound(t.narr, nentries, members_cap)), 1), dtype=torch.uint8, device=dev)
+    scr = torch.empty(max(int(dll.pz_wire_committees_scratch_bytes(t.narr, nentries, members_cap)), 16), dtype=torch.uint8,
+                      device=dev)
+    result = torch.empty(2, dtype=torch.int64, device=dev)
+    _lib.lib.call("pz_dev_wire_committees", _lib.ctypes.byref(t), nentries, members_cap, field_num, out.data_ptr(),
+                  result.data_ptr(), scr.data_ptr(), _lib.stream_ptr(dev))
+    return out, result
