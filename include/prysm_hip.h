@@ -787,8 +787,11 @@ int pz_attestation_messages(const pz_att_msg_batch* b);   /* host pointers, sync
  * Scope: the rows tallied are those with status[i] == PZ_ATT_PROCESSED and, when take is given,
  * take[i] != 0.  The reference also tallies the FAILED attestations of a block whose last
  * attestation passed (service.go:304-318 looks only at the last error), re-deriving their parents
- * and committee; the chain engine does that, this batched form does not: a caller leaves such
- * blocks to the engine (prysm_amd.blockchain.tally_serialized_blocks reports them).  A row also
+ * and committee.  That decision is the block gate's (pz_dev_block_gate below): its vote_status
+ * column reads PZ_ATT_PROCESSED on exactly the rows the reference tallies, with committee and
+ * parents_start completed for the re-derived ones, and is passed here as `status`; a caller that
+ * passes the checks' status instead tallies the passed rows only
+ * (prysm_amd.blockchain.tally_serialized_blocks, tally_mixed).  A row also
  * contributes nothing, and nothing is read through its offsets, when m > 64, when
  * parents_start[i] + 64 - m > n_recent (the checks never report either as PROCESSED), when the
  * n_oblique column disagrees with oblique_first, or when committee[i] >= ncomm, which sets the
@@ -855,6 +858,65 @@ int pz_dev_vote_cache_lookup(pz_vote_cache* cache, const uint8_t* d_hashes, uint
  * stream of the cache's last call first. */
 int pz_vote_cache_lookup(pz_vote_cache* cache, const uint8_t* hashes, uint64_t n, uint64_t* totals,
                          uint32_t* slots /* optional */);
+
+/* ---- T/R: the block gate: which blocks go on, which rows reach the cache and the pool -----------
+ * blockProcessing looks only at the LAST attestation's error (blockchain/service.go:281-306), then
+ * runs calculateBlockVoteCache over EVERY attestation of the block (service.go:313-318, core.go:
+ * 300-345), the ones processAttestation refused included, and appends the ones that passed to
+ * processedAttestations (service.go:299).  For a batch of decoded blocks (block b's rows are
+ * att_first[b] .. att_first[b+1] of the attestation columns, n_rows of them):
+ *
+ * block b is ACCEPTED iff block_status[b] == PZ_OK and rec_status (when given) is PZ_OK on every
+ * one of its rows; it is OPEN iff it is accepted, n_rows > 0 and its last row's check status is
+ * PZ_ATT_PROCESSED.  report[b] = 0 not open, 1 open with every row PROCESSED, 2 open with some row
+ * not PROCESSED.  A block whose att_first pair is inverted or runs past chk.natt is rejected, and
+ * nothing is read or written through it.
+ *
+ * vote_status[i] is PZ_ATT_PROCESSED exactly where the reference tallies row i.  In an open block,
+ * by the row's check status:
+ *   PROCESSED, BITFIELD_LEN, TRAILING_BITS  tallied with the checks' committee / parents_start
+ *                   (CheckBit ignores the bits past the committee and panics past the bitfield,
+ *                   core.go:328-331: the tally raises that panic when a parent is not skipped);
+ *   NO_COMMITTEE    getAttesterIndices returns an error (core.go:373): keeps its status;
+ *   SLOT_HIGH, SLOT_LOW, JUSTIFIED  re-derived, in u64 arithmetic that wraps: start = bs - slot,
+ *                   end = start - m + 64; start > end or end > n_recent: Go panics (core.go:353);
+ *                   idx = slot - last_state_recalc >= narr: Go panics (core.go:367); else array
+ *                   idx is walked for the shard: found, committee[i] and parents_start[i] = start
+ *                   are written over the checks' and the row is tallied; not found, it keeps its
+ *                   status (core.go:373);
+ *   PZ_ERANGE, PZ_EINDEX  processAttestation itself panicked: the panic bit, in any accepted block,
+ *                   open or not.
+ * In a block that is not open nothing is tallied: a PROCESSED row reads PZ_ATT_NOT_PROCESSED,
+ * every other row keeps its check status.  pend_take[i] = 1 iff row i is PROCESSED, its block is
+ * open and candidate[b] != 0 (when given: the walk's decision that block b reaches
+ * computeNewActiveState, service.go:261-269, :331-333).  flags: one word the caller zeroes, ORed:
+ * bit 0 = the reference panics on some row (the other outputs are filled all the same).
+ *
+ * One launch, one wave per block; no scratch.  Of chk it reads natt, status, slot,
+ * block_slot, n_oblique, shard_id, last_state_recalc, n_recent and the table (narr, arr_offs,
+ * arr_shard, arr_comm), and writes committee and parents_start.
+ * PZ_EINVAL, before any launch: a NULL batch; nblocks >= 2^31; with nblocks > 0 a NULL att_first,
+ * block_status, report, vote_status, flags, chk.committee or chk.parents_start, with chk.natt > 0
+ * a NULL column of those read, with chk.narr > 0 a NULL table.  nblocks == 0 launches nothing. */
+typedef struct pz_block_gate_batch {   /* every member a pointer, a uint64_t or the embedded batch */
+  uint64_t nblocks;
+  const uint64_t* att_first;     /* nblocks + 1 (pz_unwire_blocks) */
+  const int32_t*  block_status;  /* nblocks: the decoder's top-level status */
+  const int32_t*  rec_status;    /* optional, chk.natt: pz_attestation_cols_out.status */
+  const uint8_t*  candidate;     /* optional, nblocks */
+  pz_att_check_batch chk;        /* the columns and state the checks read, and their three outputs,
+                                    already filled by pz_[dev_]check_attestations; committee and
+                                    parents_start are completed in place for re-derived rows */
+  uint8_t*  report;              /* nblocks: 0 / 1 / 2 */
+  int32_t*  vote_status;         /* chk.natt: feed it to pz_vote_cols_batch.status */
+  uint8_t*  pend_take;           /* optional, chk.natt: feed it to pz_dev_att_pool_append */
+  uint32_t* flags;               /* one word, ORed: bit 0 = the reference panics */
+} pz_block_gate_batch;
+/* service.go:281-318 over device pointers, on the caller's stream, asynchronous. */
+int pz_dev_block_gate(const pz_block_gate_batch* b, void* stream);
+/* service.go:281-318 over host pointers, synchronous; returns PZ_EINDEX when bit 0 of *flags is
+ * set, the outputs filled all the same.  A row no block names comes back as it was. */
+int pz_block_gate(const pz_block_gate_batch* b);
 
 /* ---- R: ActiveState.PendingAttestations resident on the device --------------------------------
  * The attestations a block contributes (processedAttestations, blockchain/service.go:280-301)

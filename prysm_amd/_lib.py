@@ -117,6 +117,8 @@ SIGNATURES = {
     "pz_vote_cache_voters": [vp, vp, vp, c_intp],
     "pz_dev_vote_cache_lookup": [vp, vp, u64, vp, vp, vp],
     "pz_vote_cache_lookup": [vp, vp, u64, vp, vp],
+    "pz_dev_block_gate": [vp, vp],
+    "pz_block_gate": [vp],
     "pz_att_pool_new": [vp, ctypes.c_int, vp],
     "pz_att_pool_free": [vp],
     "pz_att_pool_scratch_bytes": [u64],
@@ -285,6 +287,14 @@ class VoteColsBatch(ctypes.Structure):
         ("n_oblique_total", u64), ("bits", vp), ("boffs", vp), ("status", vp), ("committee", vp),
         ("parents_start", vp), ("take", vp), ("recent", vp), ("n_recent", u64), ("members", vp), ("coffs", vp),
         ("ncomm", u64), ("balance", vp),
+    ]
+
+
+class BlockGateBatch(ctypes.Structure):
+    """Mirror of ``pz_block_gate_batch`` (include/prysm_hip.h)."""
+    _fields_ = [
+        ("nblocks", u64), ("att_first", vp), ("block_status", vp), ("rec_status", vp), ("candidate", vp),
+        ("chk", AttCheckBatch), ("report", vp), ("vote_status", vp), ("pend_take", vp), ("flags", vp),
     ]
 
 

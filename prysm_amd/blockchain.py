@@ -108,7 +108,8 @@ def _split_decode_check(payload, offsets, last_justified_slot, last_state_recalc
     (``pz_dev_check_attestations``).  Only the attestation count visits the host.  Returns the
     device tensors: ``d_bytes``, ``d_offs``, ``blk``, ``att``, ``natt`` (an int), ``rec`` (the
     records' decode statuses), ``status`` (the checks' statuses with ``rec`` folded in, natt rows),
-    ``committee`` (or None), ``parents_start`` and ``block_status`` (folded)."""
+    ``committee`` (or None), ``parents_start`` and ``block_status`` (folded) -- and, for the block
+    gate, ``chk`` (the checks' batch) and ``table`` (the committee table's device tensors)."""
     import torch
 
     dev = torch.device("cuda", device)
@@ -132,7 +133,8 @@ def _split_decode_check(payload, offsets, last_justified_slot, last_state_recalc
     status = torch.where(rec != 0, rec, status[:natt])
     block_status = wire.folded_block_status(blk["status"], blk["att_block"][:natt], rec)
     return {"dev": dev, "n": n, "d_bytes": d_bytes, "d_offs": d_offs, "blk": blk, "att": att, "natt": natt, "rec": rec,
-            "status": status, "committee": comm, "parents_start": pstart, "block_status": block_status}
+            "status": status, "committee": comm, "parents_start": pstart, "block_status": block_status,
+            "chk": b, "table": table}
 
 
 def check_serialized_blocks(data, offsets, last_justified_slot, last_state_recalc, n_recent, shard_and_committees,
@@ -329,8 +331,55 @@ def pend_serialized_blocks(pool, data, offsets, last_justified_slot, last_state_
     return (open_.cpu().numpy(), d["blk"]["att_first"].cpu().numpy().view(np.uint64), d["status"].cpu().numpy())
 
 
+def _gate(d, candidate=None):
+    """``pz_dev_block_gate`` over :func:`_split_decode_check`'s tensors, on the current stream.
+    Returns ``(word, report, vote_status, pend_take, flags)``: ``word`` is the one uint8 buffer
+    ``flags`` (its first four bytes) and ``report`` (the rest) are views of, so that one copy
+    brings both to the host."""
+    import torch
+
+    dev, n, natt, blk, att = d["dev"], d["n"], d["natt"], d["blk"], d["att"]
+    if d["committee"] is None:
+        raise PzError(_lib.PZ_EINVAL, "the block gate completes the committee column: decode with want_committee")
+    word = torch.zeros(4 + n, dtype=torch.uint8, device=dev)
+    flags, report = word[:4].view(torch.int32), word[4:]
+    status = d["status"].contiguous()
+    vote_status = torch.empty(max(natt, 1), dtype=torch.int32, device=dev)
+    pend_take = torch.empty(max(natt, 1), dtype=torch.uint8, device=dev)
+    cand = None if candidate is None else _to_device(np.ascontiguousarray(candidate, dtype=np.uint8), dev)
+    if cand is not None and cand.numel() != n:
+        raise PzError(_lib.PZ_EINVAL, "candidate holds %d entries for %d blocks" % (cand.numel(), n))
+    chk, p = d["chk"], _lib.dptr
+    chk = _lib.AttCheckBatch(
+        natt=natt, slot=p(att["slot"]), shard_id=p(att["shard_id"]), n_oblique=p(att["n_oblique"]),
+        block_slot=p(blk["att_block_slot"]), last_state_recalc=chk.last_state_recalc, n_recent=chk.n_recent,
+        narr=chk.narr, arr_offs=chk.arr_offs, arr_shard=chk.arr_shard, arr_comm=chk.arr_comm, coffs=chk.coffs,
+        status=p(status), committee=p(d["committee"]), parents_start=p(d["parents_start"]))
+    b = _lib.BlockGateBatch(nblocks=n, att_first=p(blk["att_first"]), block_status=p(blk["status"]),
+                            rec_status=p(d["rec"]), candidate=p(cand), chk=chk, report=p(report),
+                            vote_status=p(vote_status), pend_take=p(pend_take), flags=p(flags))
+    lib.call("pz_dev_block_gate", ctypes.byref(b), _lib.stream_ptr(dev))
+    return word, report, vote_status[:natt], pend_take[:natt], flags
+
+
+def gate_blocks(d, candidate=None):
+    """The block gate (``pz_dev_block_gate``, prysm_amd/csrc/blockgate.hip) over
+    :func:`_split_decode_check`'s tensors ``d``, on the current stream: which blocks are open
+    (service.go:281-306), which rows calculateBlockVoteCache tallies (service.go:313-318 runs over
+    every attestation of an open block, the refused ones included) and which reach
+    processedAttestations.  Returns the device tensors ``(report, vote_status, pend_take, flags)``:
+    ``report`` uint8 per block (BLOCK_REJECTED / BLOCK_TALLIED / BLOCK_MIXED), ``vote_status`` int32
+    per row (PZ_ATT_PROCESSED exactly where the reference tallies the row: the tally's ``status``),
+    ``pend_take`` uint8 per row (the pool's ``take``; ``candidate`` as in
+    :func:`pend_serialized_blocks`) and ``flags`` (one int32; bit 0: the reference panics).
+    ``d["committee"]`` and ``d["parents_start"]`` are completed in place for the re-derived rows.
+    Nothing visits the host."""
+    return _gate(d, candidate)[1:]
+
+
 def tally_serialized_blocks(cache, data, offsets, last_justified_slot, last_state_recalc, n_recent,
-                            shard_and_committees, recent_hashes, balance, device=0, pending=None, candidate=None):
+                            shard_and_committees, recent_hashes, balance, device=0, pending=None, candidate=None,
+                            tally_mixed=False):
     """The T side of blockProcessing (blockchain/service.go:313-318: calculateBlockVoteCache over
     a block's attestations, core.go:300-345) for a batch of received blocks held as bytes, against
     one chain state, into ``cache`` (a ``prysm_amd.votes.DeviceVoteCache``): the same upload, split,
@@ -350,7 +399,17 @@ def tally_serialized_blocks(cache, data, offsets, last_justified_slot, last_stat
 
     With ``pending`` (a ``prysm_amd.pending.DevicePendingAttestations``) the same decode also feeds
     the pool, as :func:`pend_serialized_blocks` does (``candidate`` as there; it bears on the pool
-    alone): one upload then serves both.  With ``pending=None`` nothing about this function changes."""
+    alone): one upload then serves both.  With ``pending=None`` nothing about this function changes.
+
+    With ``tally_mixed=True`` the decision is the block gate's (:func:`gate_blocks`): a mixed block is
+    tallied as the reference tallies it, its refused attestations included (their parents and
+    committee re-derived on the device), so the cache is exact on every block the reference
+    tallies; the report still says 0 / 1 / 2.  Where the reference would panic on some row of the
+    batch (a slice bound or committee index of the re-derivation, or processAttestation's own),
+    ``ChainPanic`` is raised and neither the cache nor the pool sees any of the batch: it lands whole
+    or panics.  The price is one more host read -- the gate's flag word and report, in one copy --
+    between the gate and the tally.  (A panic only the tally can find, CheckBit past a short
+    bitfield, stays the cache's sticky PZ_EINDEX, as without the gate.)"""
     import torch
 
     data = np.ascontiguousarray(_lib.as_u8(data), dtype=np.uint8)
@@ -363,6 +422,21 @@ def tally_serialized_blocks(cache, data, offsets, last_justified_slot, last_stat
     dev, n, natt, blk, status = d["dev"], d["n"], d["natt"], d["blk"], d["status"]
     first = blk["att_first"]
     report = torch.zeros(n, dtype=torch.int64, device=dev)
+    if tally_mixed:
+        word, report, vote_status, pend_take, _ = _gate(d, candidate if pending is not None else None)
+        host = word.cpu().numpy()  # the one extra read: flags, then the report
+        if host[:4].view(np.uint32)[0] & 1:
+            raise ChainPanic("a block of the batch makes the reference panic (processAttestation or "
+                             "calculateBlockVoteCache: slice bounds, core.go:353, or committee index, core.go:367)")
+        if natt:
+            members = np.ascontiguousarray([v for arr in shard_and_committees for e in arr for v in e[1]] or [0],
+                                           dtype=np.uint32)
+            cache.tally_columns(d["att"], natt, vote_status, d["committee"], d["parents_start"], _to_device(recent, dev),
+                                _to_device(members, dev), d["table"][3],
+                                _to_device(np.ascontiguousarray(balance, dtype=np.uint64), dev))
+            if pending is not None:
+                pending.append_columns(d["att"], natt, status.contiguous(), d["committee"], take=pend_take)
+        return (host[4:].astype(np.int64), first.cpu().numpy().view(np.uint64), status.cpu().numpy())
     if natt:
         open_, att_block, count, nproc = _open_blocks(d)
         report = open_.long() * (BLOCK_TALLIED + (BLOCK_MIXED - BLOCK_TALLIED) * (nproc != count).long())

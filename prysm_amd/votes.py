@@ -77,8 +77,10 @@ class DeviceVoteCache(_lib.Handle):
 
     Scope, as the header states it: a tally covers the rows whose ``status`` is PZ_ATT_PROCESSED
     (and ``take[i] != 0`` when ``take`` is given).  The reference also tallies the failed
-    attestations of a block whose last attestation passed; that is the engine's job
-    (``blockchain.tally_serialized_blocks`` reports such blocks and leaves them out).
+    attestations of a block whose last attestation passed; which rows those are is the block
+    gate's decision (``blockchain.gate_blocks``: its ``vote_status`` goes in as ``status``), and
+    ``blockchain.tally_serialized_blocks`` reports such blocks and, with ``tally_mixed``, tallies
+    them that way.
 
     The read side is ``VoteCache``'s: ``items()``, ``voters(h)``, ``total(h)``, ``h in cache``.  A
     panic of the reference (PZ_EINDEX) or a call dropped for capacity (PZ_ERANGE) is sticky and
