@@ -918,6 +918,113 @@ int pz_dev_block_gate(const pz_block_gate_batch* b, void* stream);
  * set, the outputs filled all the same.  A row no block names comes back as it was. */
 int pz_block_gate(const pz_block_gate_batch* b);
 
+/* ---- R: ActiveState.RecentBlockHashes resident on the device --------------------------------------
+ * The ring of the last 128 block hashes (types/state.go:45-49, 189-195) that computeNewActiveState
+ * rolls by one for every candidate block (blockchain/core.go:223-237), in place on the object
+ * c.chain.ActiveState() returns (service.go:346).  The handle owns 129 entries of 32 bytes
+ * (common.BytesToHash-normalised) with a stored length each (u8; a genesis entry has length 0: what
+ * pz_dev_active_state_bytes' d_recent_len wants): entry 0 is one hash of history, entries 1..128 are
+ * the window.  The history entry is there because the block after a transition block is still
+ * checked and tallied against the ring as it was before the transition block's hash went in
+ * (updateHead, service.go:320-321, runs after :281-318).  Two buffer sets ping-pong, as the pool's
+ * do: every append and every walk writes the other set and swaps.  Calls on one ring are ordered by
+ * the caller (one stream, or its own events).  Thread-safe per handle.
+ *
+ * pz_recent_hashes_new: types.NewGenesisStates' ring (types/state.go:45-49) or a later one, n == 128
+ * hashes with their stored lengths (lens NULL: all 32; a length above 32 counts as 32); the history
+ * entry starts as zeros.  A chain from genesis always holds 128 (core.go:230-232): any other n is
+ * PZ_EINVAL, and a shorter ring stays with the one-state functions. */
+typedef struct pz_recent_hashes pz_recent_hashes;
+int  pz_recent_hashes_new(const uint8_t* hashes, const uint8_t* lens, uint64_t n, int device, pz_recent_hashes** out);
+void pz_recent_hashes_free(pz_recent_hashes* ring);
+/* RecentBlockHashes() (types/state.go:189-195) as device pointers to the live set's window (128 x 32
+ * bytes, 16-byte aligned) and its 128 lengths, valid until the ring's next append or walk: pass them
+ * as they are to pz_dev_state_recalc (recent), pz_dev_active_state_bytes (d_recent, d_recent_len),
+ * pz_vote_cols_batch.recent and pz_att_msg_batch.recent.  Either output may be NULL.  No device call. */
+int  pz_recent_hashes_view(pz_recent_hashes* ring, const uint8_t** d_hashes, const uint8_t** d_lens);
+/* Host download of all 129 entries (RecentBlockHashes(), types/state.go:189-195, behind the history
+ * entry) and their lengths; either may be NULL.  Waits for the stream of the ring's last call. */
+int  pz_recent_hashes_read(pz_recent_hashes* ring, uint8_t* hashes /* 129 x 32 */, uint8_t* lens /* 129 */);
+/* computeNewActiveState's append (core.go:230-237) for a caller that decides for itself (the
+ * transition block's path, one-block callers): of n hashes (n x 32 bytes, 16-byte aligned), those
+ * with d_take[j] != 0 (NULL: all) are appended in order, and the last 129 entries are kept.  When
+ * any hash is taken EVERY entry's stored length becomes 32: the reference appends to
+ * RecentBlockHashes(), the [32]byte form of every entry (types/state.go:189-195), and stores that
+ * list back whole (core.go:230-236); only a ring nothing was appended to keeps its lengths.  One launch of one workgroup on the caller's stream, no scratch.  PZ_EINVAL, before any
+ * launch: a NULL ring; with n > 0 a NULL or misaligned d_hashes; n >= 2^31.  n == 0 launches nothing. */
+int  pz_dev_recent_hashes_append(pz_recent_hashes* ring, const uint8_t* d_hashes, const uint8_t* d_take /* optional */,
+                                 uint64_t n, void* stream);
+/* The same append (core.go:230-237) over host pointers (any alignment), synchronous. */
+int  pz_recent_hashes_append(pz_recent_hashes* ring, const uint8_t* hashes, const uint8_t* take /* optional */, uint64_t n);
+
+/* ---- T/R: the block walk: a run of blocks, each against its own RecentBlockHashes -----------------
+ * The sequential decisions blockProcessing takes over the blocks that go on -- updateHead and the
+ * candidate rule (blockchain/service.go:320-333), IsCycleTransition (core.go:181-183) -- as scans
+ * over a run of nblocks received blocks, and the window of RecentBlockHashes each of them reads
+ * (getSignedParentHashes, core.go:348-360): the reference appends each candidate's hash in place
+ * (core.go:223-237 on the pointer of service.go:346), so block j reads a window shifted by the
+ * number of candidates before it.
+ *
+ * go_j = report[j] != 0 (the block gate's report).  Eligibility stays the caller's: the parent is
+ * saved (service.go:261-269) and CanProcessBlock holds (:272, :308); the caller applies it by handing
+ * the gate a block_status other than PZ_OK for an ineligible block.  In block order, "pending" being
+ * has_candidate or an earlier block of the run that went on:
+ *   cand_j = go_j and (not pending, or slot_j > 1 and slot_j > the largest slot of the carried
+ *            candidate and of the earlier candidates of the run)                  (service.go:320-333)
+ *   stop   = the smallest of: the index of the first candidate with slot >= last_state_recalc + 64
+ *            (core.go:181-183; that block excluded), with lag > 0 one past the first candidate (from
+ *            the next block on the CrystallizedState differs too), and nblocks.
+ *   walk[j] = 0 not going on, 1 saved but not the candidate (:331-333), 2 candidate, 3 deferred
+ *            (j >= stop: no tally, no pool row, no hash; the caller submits it again).
+ *   base[j] = 1 - lag + (the candidates before j), 0 for a deferred block.
+ * The log is the ring's 129 entries followed by the run's candidate hashes in order, the rest of
+ * its 129 + nblocks entries zeroed; block j's window is log[base[j], base[j] + 128).  Per row i of
+ * block b = att_block[i]: parents_start[i] += base[b]; pend_take[i] &= (walk[b] == 2); where b is
+ * deferred a PZ_ATT_PROCESSED vote_status[i] becomes PZ_ATT_NOT_PROCESSED.  With the checks run at
+ * n_recent = 128 no row names a log position at or past 129 + the candidates before its block
+ * (blockwalk_dev.h has the proof), so `log` with n_recent = 129 + nblocks goes to
+ * pz_dev_vote_cache_tally and pz_dev_attestation_messages as `recent`.  Last the ring becomes the
+ * last 129 entries of the log's used part (core.go:230-232), every stored length 32 when the run
+ * had a candidate (as pz_dev_recent_hashes_append) -- unless
+ * flags is given and its bit 0 is set (the reference panics somewhere in the batch, and the caller
+ * will land none of it): then the ring's content stays as it was.
+ * result[4]: stop, the number of candidates before stop, and has_candidate / candidate_slot as
+ * they are after block stop - 1 (to carry into the next call).
+ *
+ * Three dependent launches on the caller's stream (scan, rows, roll: DESIGN.md §3); no workgroup
+ * waits for another, the host reads nothing.  PZ_EINVAL, before any launch: a NULL ring or batch;
+ * nblocks >= 2^31; lag > 1; with nblocks > 0 a NULL slot_number, report, block_hash, walk, base,
+ * result or (device form) log, a block_hash or log that is not 16-byte aligned; with natt > 0 a
+ * NULL att_block, vote_status or parents_start.  nblocks == 0 launches nothing and leaves the ring
+ * as it is.  pend_take is optional. */
+typedef struct pz_block_walk_batch {   /* every member a pointer or a uint64_t */
+  uint64_t nblocks;
+  const uint64_t* slot_number;   /* nblocks: pz_block_cols_out.slot_number */
+  const uint8_t*  report;        /* nblocks: pz_block_gate_batch.report */
+  const uint8_t*  block_hash;    /* nblocks x 32: Block.Hash(), pz_dev_blake2b512_spans over the blocks */
+  uint64_t has_candidate, candidate_slot;   /* carried in: candidateBlock != nilBlock, its SlotNumber */
+  uint64_t last_state_recalc;    /* CrystallizedState.LastStateRecalc as IsCycleTransition reads it, after
+                                    updateHead (service.go:320-321, :345): with lag, the new state's */
+  uint64_t lag;                  /* 1: the run starts right after a transition block (see the ring) */
+  uint64_t natt;
+  const uint32_t* att_block;     /* natt: pz_block_cols_out.att_block */
+  int32_t*  vote_status;         /* natt: pz_block_gate_batch.vote_status, narrowed in place */
+  uint8_t*  pend_take;           /* optional, natt: pz_block_gate_batch.pend_take, narrowed in place */
+  uint64_t* parents_start;       /* natt: pz_att_check_batch.parents_start, made absolute in place */
+  uint8_t*  walk;                /* nblocks */
+  uint64_t* base;                /* nblocks */
+  uint64_t* result;              /* 4 */
+  uint8_t*  log;                 /* pz_block_walk_scratch_bytes(nblocks, natt) bytes: (129 + nblocks) x 32 */
+  const uint32_t* flags;         /* optional: pz_block_gate_batch.flags; with bit 0 set the ring stays as it is */
+} pz_block_walk_batch;
+/* The bytes of `log` (no reference counterpart). */
+uint64_t pz_block_walk_scratch_bytes(uint64_t nblocks, uint64_t natt);
+/* service.go:320-333 over a run, device pointers, on the caller's stream, asynchronous. */
+int pz_dev_block_walk(pz_recent_hashes* ring, const pz_block_walk_batch* b, void* stream);
+/* service.go:320-333 over a run, host pointers (any alignment), synchronous; waits for the stream
+ * of the ring's last call first.  log is optional here. */
+int pz_block_walk(pz_recent_hashes* ring, const pz_block_walk_batch* b);
+
 /* ---- R: ActiveState.PendingAttestations resident on the device --------------------------------
  * The attestations a block contributes (processedAttestations, blockchain/service.go:280-301)
  * become ActiveState.PendingAttestations (computeNewActiveState, core.go:223-237) and feed the

@@ -119,6 +119,15 @@ SIGNATURES = {
     "pz_vote_cache_lookup": [vp, vp, u64, vp, vp],
     "pz_dev_block_gate": [vp, vp],
     "pz_block_gate": [vp],
+    "pz_recent_hashes_new": [vp, vp, u64, ctypes.c_int, vp],
+    "pz_recent_hashes_free": [vp],
+    "pz_recent_hashes_view": [vp, vp, vp],
+    "pz_recent_hashes_read": [vp, vp, vp],
+    "pz_dev_recent_hashes_append": [vp, vp, vp, u64, vp],
+    "pz_recent_hashes_append": [vp, vp, vp, u64],
+    "pz_block_walk_scratch_bytes": [u64, u64],
+    "pz_dev_block_walk": [vp, vp, vp],
+    "pz_block_walk": [vp, vp],
     "pz_att_pool_new": [vp, ctypes.c_int, vp],
     "pz_att_pool_free": [vp],
     "pz_att_pool_scratch_bytes": [u64],
@@ -298,6 +307,16 @@ class BlockGateBatch(ctypes.Structure):
     ]
 
 
+class BlockWalkBatch(ctypes.Structure):
+    """Mirror of ``pz_block_walk_batch`` (include/prysm_hip.h)."""
+    _fields_ = [
+        ("nblocks", u64), ("slot_number", vp), ("report", vp), ("block_hash", vp), ("has_candidate", u64),
+        ("candidate_slot", u64), ("last_state_recalc", u64), ("lag", u64), ("natt", u64), ("att_block", vp),
+        ("vote_status", vp), ("pend_take", vp), ("parents_start", vp), ("walk", vp), ("base", vp), ("result", vp),
+        ("log", vp), ("flags", vp),
+    ]
+
+
 class RecalcBatch(ctypes.Structure):
     """Mirror of ``pz_recalc_batch`` (include/prysm_hip.h)."""
     _fields_ = [
@@ -331,6 +350,7 @@ _RESTYPES = {"pz_last_error": ctypes.c_char_p, "pz_chain_free": None, "pz_set_se
              "pz_unwire_attestations_scratch_bytes": u64, "pz_unwire_blocks_scratch_bytes": u64,
              "pz_vote_cache_free": None, "pz_vote_cache_scratch_bytes": u64,
              "pz_att_pool_free": None, "pz_att_pool_scratch_bytes": u64,
+             "pz_recent_hashes_free": None, "pz_block_walk_scratch_bytes": u64,
              "pz_recalc_state_free": None, "pz_state_recalc_scratch_bytes": u64,
              "pz_wire_committees_bound": u64, "pz_wire_committees_scratch_bytes": u64,
              "pz_crystallized_state_bound": u64, "pz_crystallized_state_scratch_bytes": u64, "pz_active_state_bound": u64}

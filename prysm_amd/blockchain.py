@@ -331,18 +331,19 @@ def pend_serialized_blocks(pool, data, offsets, last_justified_slot, last_state_
     return (open_.cpu().numpy(), d["blk"]["att_first"].cpu().numpy().view(np.uint64), d["status"].cpu().numpy())
 
 
-def _gate(d, candidate=None):
+def _gate(d, candidate=None, block_status=None, head=0, tail=0):
     """``pz_dev_block_gate`` over :func:`_split_decode_check`'s tensors, on the current stream.
     Returns ``(word, report, vote_status, pend_take, flags)``: ``word`` is the one uint8 buffer
-    ``flags`` (its first four bytes) and ``report`` (the rest) are views of, so that one copy
-    brings both to the host."""
+    ``flags`` (four bytes) and ``report`` (the n after them) are views of, so that one copy
+    brings both to the host; ``head`` / ``tail`` bytes before and after them are the caller's, to
+    come along in that copy.  ``block_status`` (int32 per block) replaces the decoder's."""
     import torch
 
     dev, n, natt, blk, att = d["dev"], d["n"], d["natt"], d["blk"], d["att"]
     if d["committee"] is None:
         raise PzError(_lib.PZ_EINVAL, "the block gate completes the committee column: decode with want_committee")
-    word = torch.zeros(4 + n, dtype=torch.uint8, device=dev)
-    flags, report = word[:4].view(torch.int32), word[4:]
+    word = torch.zeros(head + 4 + n + tail, dtype=torch.uint8, device=dev)
+    flags, report = word[head:head + 4].view(torch.int32), word[head + 4:head + 4 + n]
     status = d["status"].contiguous()
     vote_status = torch.empty(max(natt, 1), dtype=torch.int32, device=dev)
     pend_take = torch.empty(max(natt, 1), dtype=torch.uint8, device=dev)
@@ -355,7 +356,8 @@ def _gate(d, candidate=None):
         block_slot=p(blk["att_block_slot"]), last_state_recalc=chk.last_state_recalc, n_recent=chk.n_recent,
         narr=chk.narr, arr_offs=chk.arr_offs, arr_shard=chk.arr_shard, arr_comm=chk.arr_comm, coffs=chk.coffs,
         status=p(status), committee=p(d["committee"]), parents_start=p(d["parents_start"]))
-    b = _lib.BlockGateBatch(nblocks=n, att_first=p(blk["att_first"]), block_status=p(blk["status"]),
+    b = _lib.BlockGateBatch(nblocks=n, att_first=p(blk["att_first"]),
+                            block_status=p(blk["status"] if block_status is None else block_status),
                             rec_status=p(d["rec"]), candidate=p(cand), chk=chk, report=p(report),
                             vote_status=p(vote_status), pend_take=p(pend_take), flags=p(flags))
     lib.call("pz_dev_block_gate", ctypes.byref(b), _lib.stream_ptr(dev))
@@ -456,6 +458,114 @@ class ChainPanic(RuntimeError):
     """The reference would panic here (index out of range / nil map / nil state)."""
 
 
+WALK_OFF, WALK_SAVED, WALK_CANDIDATE, WALK_DEFERRED = 0, 1, 2, 3  # walk_serialized_blocks' per-block code
+_INELIGIBLE = 1  # a block status that is not PZ_OK: the parent is not saved or CanProcessBlock fails
+
+
+def walk_serialized_blocks(cache, pool, ring, data, offsets, last_justified_slot, last_state_recalc,
+                           shard_and_committees, balance, eligible=None, has_candidate=False, candidate_slot=0, lag=0,
+                           want_digests=False, device=0):
+    """blockProcessing (blockchain/service.go:229-363) for a RUN of consecutive received blocks held
+    as bytes, each against its own RecentBlockHashes, in one call: into ``cache`` (a
+    ``prysm_amd.votes.DeviceVoteCache``), ``pool`` (a ``prysm_amd.pending.DevicePendingAttestations``)
+    and ``ring`` (a ``prysm_amd.pending.DeviceRecentHashes``).  The reference appends every candidate
+    block's hash to RecentBlockHashes in place (computeNewActiveState, core.go:223-237, on the pointer
+    of service.go:346), so block k reads a window shifted by the candidates before it
+    (getSignedParentHashes, core.go:348-360): the other ``*_serialized_blocks`` functions work against
+    ONE chain state and are exact for one block at a time only.
+
+    After one upload: split, decode and checks with ``n_recent = 128`` (the statuses read only the
+    ring's length, which a chain from genesis never changes); the block gate, with ``eligible`` (one
+    0/1 per block, None: all; the caller's parent check, service.go:261-269, and CanProcessBlock,
+    :272, :308) folded into its block status on the device; Block.Hash over the blocks
+    (``pz_dev_blake2b512_spans``); the walk (``pz_dev_block_walk``: the candidate rule of
+    service.go:320-333 as scans, the rows' ``parents_start`` made absolute in the log ``[ring | this
+    run's candidate hashes]``, the ring rolled); ONE host read -- the gate's flag word and report with
+    the walk's result record and codes; then ``cache.tally_columns`` and ``pool.append_columns`` over
+    the log, and with ``want_digests`` the processAttestation message digests over it.  No hash list
+    comes from the host.
+
+    ``has_candidate`` / ``candidate_slot``: the candidate block pending before the run (carry the
+    returned pair into the next call).  The run stops before the first candidate that is a cycle
+    transition (``slot >= last_state_recalc + 64``, core.go:181-183), which the caller handles with
+    ``state_recalc_resident``; the call right after a transition block takes ``lag=1`` with the
+    pre-transition scalars, table and balances, and stops one past its first candidate.  Blocks at or
+    past ``stop`` are untouched (walk code 3): submit them again.
+
+    Where the reference would panic on some row of the run ``ChainPanic`` is raised and nothing lands:
+    neither cache, pool nor ring.  Returns a dict: ``walk`` (uint8 per block, WALK_*), ``report`` (the
+    gate's), ``stop``, ``ncand``, ``has_candidate``, ``candidate_slot``, ``att_first``, ``att_status``
+    (the checks' statuses), ``parents_start`` (absolute: positions in the log), ``block_hash`` (n, 32)
+    and, with ``want_digests``, ``msg`` (natt, 64) / ``msg_len``: zero for a row that is not PROCESSED
+    or whose block is ineligible or deferred."""
+    import torch
+
+    data = np.ascontiguousarray(_lib.as_u8(data), dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    if lag not in (0, 1):
+        raise PzError(_lib.PZ_EINVAL, "lag %r: 0 or 1" % (lag,))
+    # (the span hash reads whole dwords: 4 bytes of slack after the last block)
+    payload = np.concatenate([data[:int(offsets[-1])] if n else data[:0], np.zeros(4, np.uint8)])
+    d = _split_decode_check(payload, offsets, last_justified_slot, last_state_recalc, 128, shard_and_committees, device,
+                            want_committee=True)
+    dev, natt, blk, status = d["dev"], d["natt"], d["blk"], d["status"]
+    block_status = blk["status"]
+    if eligible is not None:
+        el = _to_device(np.ascontiguousarray(eligible, dtype=np.uint8), dev)
+        if el.numel() != n:
+            raise PzError(_lib.PZ_EINVAL, "eligible holds %d entries for %d blocks" % (el.numel(), n))
+        block_status = torch.where(el != 0, block_status, torch.full_like(block_status, _INELIGIBLE))
+    # one buffer, one copy: the walk's result record, the gate's flags and report, the walk's codes
+    word, report, vote_status, pend_take, flags = _gate(d, None, block_status, head=32, tail=n)
+    result, walk = word[:32].view(torch.int64), word[36 + n:]
+    sh = _lib.stream_ptr(dev)
+    block_hash = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    lib.call("pz_dev_blake2b512_spans", d["d_bytes"].data_ptr(), d["d_offs"][:-1].data_ptr(), d["d_offs"][1:].data_ptr(), n,
+             block_hash.data_ptr() if n else None, 32, sh)
+    base = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    log = torch.empty(int(lib.dll.pz_block_walk_scratch_bytes(n, natt)), dtype=torch.uint8, device=dev)
+    p = _lib.dptr
+    # IsCycleTransition reads the chain's CrystallizedState AFTER updateHead (service.go:320-321, :345):
+    # right after a transition block that is the new one, a cycle on, while the checks above read the old
+    walk_lsr = (int(last_state_recalc) + (64 if lag else 0)) & ((1 << 64) - 1)
+    b = _lib.BlockWalkBatch(nblocks=n, slot_number=p(blk["slot_number"]), report=p(report), block_hash=p(block_hash),
+                            has_candidate=int(bool(has_candidate)), candidate_slot=int(candidate_slot),
+                            last_state_recalc=walk_lsr, lag=int(lag), natt=natt, att_block=p(blk["att_block"]),
+                            vote_status=p(vote_status), pend_take=p(pend_take), parents_start=p(d["parents_start"]),
+                            walk=p(walk), base=p(base), result=p(result), log=p(log), flags=p(flags))
+    lib.call("pz_dev_block_walk", ring._h, ctypes.byref(b), sh)
+    host = word.cpu().numpy()  # the one read
+    if host[32:36].view(np.uint32)[0] & 1:
+        raise ChainPanic("a block of the run makes the reference panic (processAttestation or "
+                         "calculateBlockVoteCache: slice bounds, core.go:353, or committee index, core.go:367)")
+    if n:
+        stop, ncand, has, cslot = (int(x) for x in host[:32].view(np.uint64))
+    else:
+        stop, ncand, has, cslot = 0, 0, int(bool(has_candidate)), int(candidate_slot) if has_candidate else 0
+    out = {"walk": host[36 + n:].copy(), "report": host[36:36 + n].copy(), "stop": stop, "ncand": ncand,
+           "has_candidate": bool(has), "candidate_slot": cslot}
+    if natt:
+        members = np.ascontiguousarray([v for arr in shard_and_committees for e in arr for v in e[1]] or [0], dtype=np.uint32)
+        cache.tally_columns(d["att"], natt, vote_status, d["committee"], d["parents_start"], log, _to_device(members, dev),
+                            d["table"][3], _to_device(np.ascontiguousarray(balance, dtype=np.uint64), dev))
+        pool.append_columns(d["att"], natt, status.contiguous(), d["committee"], take=pend_take)
+    if want_digests:
+        if natt:
+            att_block = blk["att_block"][:natt].long()
+            ran = (walk[att_block] != WALK_DEFERRED) & (block_status[att_block] == _lib.PZ_OK)
+            msg_status = torch.where(ran, status, torch.full_like(status, ATT_NOT_PROCESSED)).contiguous()
+            msg, msg_len = attestation_messages_device(d["att"], natt, msg_status, d["parents_start"], log, 129 + n)
+            out["msg"], out["msg_len"] = msg.cpu().numpy(), msg_len.cpu().numpy().view(np.uint32)
+        else:
+            out["msg"], out["msg_len"] = np.zeros((0, 64), np.uint8), np.zeros(0, np.uint32)
+    out["att_first"] = blk["att_first"].cpu().numpy().view(np.uint64)
+    out["att_status"] = status.cpu().numpy()
+    out["parents_start"] = d["parents_start"][:natt].cpu().numpy().view(np.uint64)
+    out["block_hash"] = block_hash.cpu().numpy()
+    return out
+
+
 def state_recalc_device(pool, cache, state, recent_hashes, block_slot):
     """stateRecalc (blockchain/core.go:398-497) composed from what lives on the device: ``pool`` (a
     ``prysm_amd.pending.DevicePendingAttestations``: ActiveState.PendingAttestations), ``cache`` (a
@@ -482,8 +592,10 @@ def state_recalc_device(pool, cache, state, recent_hashes, block_slot):
     from prysm_amd import pb
 
     M64 = (1 << 64) - 1
+    from prysm_amd.pending import recent_of
+
     lsr = state.last_state_recalc
-    recent = _recent_array(recent_hashes)
+    recent = _recent_array(recent_of(recent_hashes)[0])
     if len(recent) < 64:
         raise ChainPanic("stateRecalc: RecentBlockHashes()[i], index out of range (core.go:413)")
     totals = cache.items() if cache is not None else {}
@@ -546,18 +658,24 @@ def state_recalc_resident(pool, cache, state, recent_hashes, block_slot):
     lives on the device: ``pool`` (a ``prysm_amd.pending.DevicePendingAttestations``), ``cache`` (a
     ``prysm_amd.votes.DeviceVoteCache``, looked up on the device -- the map is not downloaded; None:
     no entry) and ``state`` (a ``prysm_amd.pending.ResidentRecalcState``, advanced in place).
-    ``recent_hashes`` = RecentBlockHashes() and ``block_slot`` = the transition block's SlotNumber.
-    Computes what ``state_recalc_device`` computes and raises ``ChainPanic`` where it does; a
+    ``recent_hashes`` = RecentBlockHashes() (a list, an array, or a
+    ``prysm_amd.pending.DeviceRecentHashes``, read where it lies) and ``block_slot`` = the transition
+    block's SlotNumber.  Computes what ``state_recalc_device`` computes and raises ``ChainPanic`` where it does; a
     pending ShardBlockHash longer than the state's ``hash_stride`` is refused whole (PZ_ERANGE).
     Returns the winners (one attestation row per record, 0xFFFFFFFF: none)."""
     import torch
 
+    from prysm_amd.pending import DeviceRecentHashes
+
     dev = state.balance.device
-    recent = _recent_array(recent_hashes)
-    d_recent = _to_device(recent if len(recent) else np.zeros((1, 32), np.uint8), dev)
+    if isinstance(recent_hashes, DeviceRecentHashes):  # read where it lies: nothing is uploaded
+        d_recent, n_recent = recent_hashes.view()[0], recent_hashes.WINDOW
+    else:
+        recent = _recent_array(recent_hashes)
+        d_recent, n_recent = _to_device(recent if len(recent) else np.zeros((1, 32), np.uint8), dev), len(recent)
     b = _lib.RecalcBatch(nval=state.nval, balance=state.balance.data_ptr(), start=state.start.data_ptr(),
                          end=state.end.data_ptr(), members=state.members.data_ptr(), coffs=state.coffs.data_ptr(),
-                         recent=d_recent.data_ptr(), n_recent=len(recent), block_slot=int(block_slot))
+                         recent=d_recent.data_ptr(), n_recent=n_recent, block_slot=int(block_slot))
     nbytes = int(lib.dll.pz_state_recalc_scratch_bytes(state.nval, int(pool.caps[0]), state.nrec))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     rc = lib.dll.pz_dev_state_recalc(state._h, pool._h, cache._h if cache is not None else None, ctypes.byref(b),

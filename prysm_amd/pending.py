@@ -10,7 +10,8 @@ encodes into the stored ActiveState's field 1, and as the crosslink winners' Sha
 ``RecalcState`` is the CrystallizedState side of ``blockchain.state_recalc_device``;
 ``ResidentRecalcState`` (``pz_recalc_state``, prysm_amd/csrc/recalc.hip) is the same state with its
 scalars and crosslink records resident on the device, advanced by ``blockchain.state_recalc_resident``
-in one ABI call.
+in one ABI call.  ``DeviceRecentHashes`` (``pz_recent_hashes``, prysm_amd/csrc/blockwalk.hip) is
+ActiveState.RecentBlockHashes resident on the device, rolled by ``blockchain.walk_serialized_blocks``.
 """
 import numpy as np
 
@@ -27,6 +28,86 @@ class _Raw:
 
     def __init__(self, ptr, nbytes):
         self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+
+class DeviceRecentHashes(_lib.Handle):
+    """ActiveState.RecentBlockHashes resident on one device (``pz_recent_hashes``,
+    prysm_amd/csrc/blockwalk.hip): 129 entries of 32 bytes with a stored length each, entry 0 one
+    hash of history, entries 1..128 the window.  ``hashes``: the 128 of RecentBlockHashes (byte
+    strings of at most 32 bytes, normalised here with their lengths kept, or a (128, 32) uint8 array
+    with ``lens``); None: the genesis ring (types/state.go:45-49), 128 empty entries.  Any other
+    count is refused (PZ_EINVAL): a shorter ring stays with the functions that take a list.
+
+    Usable wherever ``recent_hashes`` is accepted next to a pool or a recalc state:
+    ``blockchain.state_recalc_resident`` / ``state_recalc_device``,
+    ``DevicePendingAttestations.active_state`` / ``active_state_root`` and
+    ``blockchain.resident_state_roots``."""
+    _FREE = "pz_recent_hashes_free"
+    WINDOW = 128
+
+    def __init__(self, hashes=None, lens=None, device=0):
+        from prysm_amd.blockchain import _recent_array
+
+        if hashes is None:
+            rows, lens = np.zeros((self.WINDOW, 32), np.uint8), np.zeros(self.WINDOW, np.uint8)
+        elif isinstance(hashes, np.ndarray):
+            rows = _recent_array(hashes)
+            lens = np.full(len(rows), 32, np.uint8) if lens is None else np.ascontiguousarray(lens, dtype=np.uint8)
+        else:
+            hashes = [bytes(h) for h in hashes]
+            rows = _recent_array(hashes)
+            lens = np.array([min(len(h), 32) for h in hashes], dtype=np.uint8) if lens is None else \
+                np.ascontiguousarray(lens, dtype=np.uint8)
+        assert lens.shape == (len(rows),)
+        self._new("pz_recent_hashes_new", _lib.ptr(rows), _lib.ptr(lens), len(rows), device)
+        self.device = device
+
+    def view(self):
+        """``(hashes (128, 32) uint8, lens (128) uint8)``: torch tensors over the live window where
+        it lies (no copy), valid until the ring's next ``append`` or walk."""
+        import torch
+
+        h, n = _lib.ctypes.c_void_p(), _lib.ctypes.c_void_p()
+        lib.call("pz_recent_hashes_view", self._h, _lib.ctypes.byref(h), _lib.ctypes.byref(n))
+        dev = torch.device("cuda", self.device)
+        return (torch.as_tensor(_Raw(h.value, 32 * self.WINDOW), device=dev).view(self.WINDOW, 32),
+                torch.as_tensor(_Raw(n.value, self.WINDOW), device=dev))
+
+    def read(self, history=False):
+        """``(hashes (128, 32) uint8, lens (128) uint8)`` as numpy arrays (``pz_recent_hashes_read``;
+        waits for the ring's last call); with ``history`` all 129 entries, the history entry first."""
+        rows, lens = np.zeros((self.WINDOW + 1, 32), np.uint8), np.zeros(self.WINDOW + 1, np.uint8)
+        lib.call("pz_recent_hashes_read", self._h, rows.ctypes.data, lens.ctypes.data)
+        return (rows, lens) if history else (rows[1:], lens[1:])
+
+    def hashes(self):
+        """RecentBlockHashes as the stored byte strings (the last ``len`` bytes of each entry)."""
+        rows, lens = self.read()
+        return [rows[i, 32 - int(lens[i]):].tobytes() for i in range(self.WINDOW)]
+
+    def append(self, d_hashes, take=None):
+        """computeNewActiveState's append (core.go:230-237): the rows of ``d_hashes`` ((n, 32) uint8,
+        a torch device tensor: on the current stream, asynchronous; or a numpy array / byte strings:
+        synchronous) with ``take[j] != 0`` (None: all) go in, in order.  Once a hash went in every
+        entry is stored with 32 bytes, as the reference stores RecentBlockHashes() back."""
+        if hasattr(d_hashes, "data_ptr"):
+            n = d_hashes.numel() // 32
+            lib.call("pz_dev_recent_hashes_append", self._h, _lib.dptr(d_hashes), _lib.dptr(take), n,
+                     _lib.stream_ptr(self.device))
+            return
+        from prysm_amd.blockchain import _recent_array
+
+        rows = _recent_array(d_hashes)
+        take = None if take is None else np.ascontiguousarray(take, dtype=np.uint8)
+        lib.call("pz_recent_hashes_append", self._h, _lib.ptr(rows), _lib.ptr(take), len(rows))
+
+
+def recent_of(recent, recent_len=None):
+    """``(rows, lens)`` on the host of what a ``recent_hashes`` argument names: a
+    ``DeviceRecentHashes`` is downloaded with its stored lengths, anything else passes through."""
+    if isinstance(recent, DeviceRecentHashes):
+        return recent.read()
+    return recent, recent_len
 
 
 class DevicePendingAttestations(_lib.Handle):
@@ -173,6 +254,7 @@ class DevicePendingAttestations(_lib.Handle):
     def _stored(self, recent, recent_len, want_root, strict):
         from prysm_amd.blockchain import _recent_array
 
+        recent, recent_len = recent_of(recent, recent_len)
         rows = _recent_array(recent)
         n = len(rows)
         lens = None if recent_len is None else np.ascontiguousarray(recent_len, dtype=np.uint8)
@@ -191,7 +273,8 @@ class DevicePendingAttestations(_lib.Handle):
         """The stored ActiveState (PersistActiveState, blockchain/core.go:161-168) encoded on the
         device: the pool as field 1, then ``recent`` = RecentBlockHashes() (byte strings, normalised
         here, or a (k, 32) uint8 array) as field 2, entry i being the last ``recent_len[i]`` bytes of
-        its row (None: all 32; the genesis state's entries are empty: all 0).
+        its row (None: all 32; the genesis state's entries are empty: all 0).  A
+        ``DeviceRecentHashes`` stands for both: its window and its stored lengths.
         ``pz_active_state_read``."""
         return self._stored(recent, recent_len, False, strict)[0]
 
@@ -384,4 +467,4 @@ for _i, _name in enumerate(ResidentRecalcState._SCALARS):
     setattr(ResidentRecalcState, _name, property(lambda self, _i=_i: self.scalar(_i, strict=False)))
 
 
-__all__ = ["DevicePendingAttestations", "RecalcState", "ResidentRecalcState", "CAPS"]
+__all__ = ["DevicePendingAttestations", "DeviceRecentHashes", "RecalcState", "ResidentRecalcState", "CAPS"]
