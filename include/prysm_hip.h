@@ -1025,6 +1025,118 @@ int pz_dev_block_walk(pz_recent_hashes* ring, const pz_block_walk_batch* b, void
  * of the ring's last call first.  log is optional here. */
 int pz_block_walk(pz_recent_hashes* ring, const pz_block_walk_batch* b);
 
+/* ---- R: the saved-block set resident on the device, and the parent check over a run ---------------
+ * hasBlock (blockchain/core.go:560-562) answers blockProcessing's first question about a received
+ * block, `hasBlock(block.ParentHash())` (service.go:261-269), from the blocks saveBlock stored
+ * (service.go:324, core.go:565-577).  The handle owns that set of 32-byte block hashes on one device:
+ * an open-addressing table with a power-of-two number of cells (at least 8), linear probing from the
+ * cell the hash's first little-endian word names, a state word per cell beside its 32 key bytes (the
+ * all-zero hash is an ordinary key), a device-side count of distinct keys and a sticky error word.
+ * Probes take at most `cells` steps; a key that finds no cell sets the capacity bit (the keys that
+ * found one stay), reported as PZ_ERANGE by pz_block_set_count / _read.  Two buffer sets: a reserve
+ * that grows rehashes into the other one on the device.  Calls on one set are ordered by the caller
+ * (one stream, or its own events).  Thread-safe per handle.
+ *
+ * pz_block_set_new: the set a chain resumes with (NewBeaconChain over a stored DB, core.go:59-95):
+ * n hashes (n x 32 bytes, host, any alignment; duplicates count once) in a table of the smallest
+ * power of two >= 2 * max(n, min_keys) cells.  PZ_EINVAL: out NULL, n > 0 with hashes NULL, n or
+ * min_keys above 2^30. */
+typedef struct pz_block_set pz_block_set;
+int  pz_block_set_new(const uint8_t* hashes, uint64_t n, uint64_t min_keys, int device, pz_block_set** out);
+void pz_block_set_free(pz_block_set* set);
+/* The number of distinct keys (no reference counterpart: the DB is not counted); waits for the stream
+ * of the set's last call.  *count is filled also when the sticky PZ_ERANGE is returned. */
+int  pz_block_set_count(pz_block_set* set, uint64_t* count);
+/* Every key, in any order (no reference counterpart: the DB is not iterated): *count receives their
+ * number, and when cap >= *count hashes receives them (cap x 32 bytes).  Waits as _count does. */
+int  pz_block_set_read(pz_block_set* set, uint8_t* hashes, uint64_t cap, uint64_t* count);
+/* hasBlock (core.go:560-562) for n hashes (n x 32 bytes, 16-byte aligned device memory): d_out[q] = 1
+ * iff hash q is a key.  One launch, a lane per query, plain loads, on the caller's stream.
+ * PZ_EINVAL, before any launch: a NULL set; with n > 0 a NULL or misaligned d_hashes or a NULL d_out;
+ * n >= 2^31.  n == 0 launches nothing. */
+int  pz_dev_block_set_contains(pz_block_set* set, const uint8_t* d_hashes, uint64_t n, uint8_t* d_out, void* stream);
+/* hasBlock (core.go:560-562) over host pointers (any alignment), synchronous. */
+int  pz_block_set_contains(pz_block_set* set, const uint8_t* hashes, uint64_t n, uint8_t* out);
+/* saveBlock's key (core.go:565-577; service.go:324) for the caller that decides for itself -- the
+ * transition block's path, one-block callers: of n hashes (n x 32 bytes, 16-byte aligned device
+ * memory) those with d_take[j] != 0 (NULL: all) become keys; a hash that is already a key, or that
+ * the call holds twice, counts once.  One launch of one workgroup on the caller's stream, no scratch:
+ * per tile of 1,024 hashes a lane claims the first empty cell of its probe with a tentative claim
+ * that carries its index, a lane that reads a claim compares against that input hash, and after a
+ * barrier the lane whose claim stands writes the key.  PZ_EINVAL as _contains (d_out apart).  The
+ * caller reserves first: with fewer than n free cells the capacity bit may be set. */
+int  pz_dev_block_set_insert(pz_block_set* set, const uint8_t* d_hashes, const uint8_t* d_take /* optional */, uint64_t n,
+                             void* stream);
+/* saveBlock's key (core.go:565-577) over host pointers (any alignment), synchronous; reserves for
+ * the n hashes itself. */
+int  pz_block_set_insert(pz_block_set* set, const uint8_t* hashes, const uint8_t* take /* optional */, uint64_t n);
+/* Room for min_keys keys (no reference counterpart: the DB grows by itself): when 2 * min_keys exceeds
+ * the cells, every key is rehashed on the device, on the caller's stream, into a table of the
+ * smallest power of two that holds them; otherwise nothing happens.  The host decides from the cell
+ * count it keeps: nothing is read back.  PZ_EINVAL: a NULL set, min_keys above 2^30. */
+int  pz_dev_block_set_reserve(pz_block_set* set, uint64_t min_keys, void* stream);
+/* The same reserve (no reference counterpart), synchronous. */
+int  pz_block_set_reserve(pz_block_set* set, uint64_t min_keys);
+
+/* The parent check (service.go:261-269) for a RUN of nblocks decoded blocks, in block order, with the
+ * blocks of the run saving each other as the reference's loop would (service.go:324):
+ *   parent_j = BytesToHash of field 1: bytes[bytes_beg[5j] .. + bytes_len[5j]) (absent: the zero hash;
+ *              a span that leaves [0, nbytes) refuses the block);
+ *   free_j   = slot_number[j] <= 1 (service.go:267);
+ *   open0_j  = block_status[j] == PZ_OK and the block gate's report over the same att_first,
+ *              rec_status and att_status is not 0: the gate would open block j if its parent is saved;
+ *   link_j   = the largest i < j with block_hash[i] == parent_j and open0_i, or none;
+ *   parent_ok[j] = free_j or parent_j is in the set or (link_j exists and saved0[link_j]);
+ *   saved0[j]    = open0_j and parent_ok[j];
+ *   block_status_out[j] = block_status[j] where parent_ok[j], else PZ_ENOTFOUND.
+ * The largest open copy suffices (blockparents_dev.h has the proof).  Hand block_status_out to
+ * pz_dev_block_gate: its report is then non-zero exactly where saved0 holds.  CanProcessBlock
+ * (service.go:272, :308) stays the caller's, folded into block_status.  The set is only read.
+ *
+ * A memset and three dependent launches on the caller's stream, whatever nblocks; no workgroup waits
+ * for another, the host reads nothing: (1) a lane per block takes open0 and enters the open blocks
+ * into a run table in scratch, keyed by block_hash; (2) a lane per block probes the set and the run
+ * table for parent_j; (3) one workgroup resolves the chains by ceil(log2 nblocks) double-buffered
+ * pointer-jumping rounds and writes the three outputs.
+ * PZ_EINVAL, before any launch: a NULL set or batch; nblocks >= 2^31; with nblocks > 0 a NULL
+ * bytes_beg, bytes_len, slot_number, block_hash, att_first, block_status, parent_ok, saved0 or
+ * block_status_out, nbytes > 0 with bytes NULL, natt > 0 with att_status NULL, (device form) a NULL or
+ * misaligned d_scratch, a block_hash that is not 16-byte aligned.  nblocks == 0 launches nothing. */
+typedef struct pz_block_parents_batch {   /* every member a pointer or a uint64_t */
+  uint64_t nblocks;
+  const uint8_t*  bytes;            /* nbytes: the received blocks (what pz_unwire_blocks split) */
+  uint64_t nbytes;
+  const uint64_t* bytes_beg;        /* nblocks*5: pz_block_cols_out.bytes_beg (entry 5j is read) */
+  const uint32_t* bytes_len;        /* nblocks*5: pz_block_cols_out.bytes_len */
+  const uint64_t* slot_number;      /* nblocks: pz_block_cols_out.slot_number */
+  const uint8_t*  block_hash;       /* nblocks x 32: Block.Hash(), pz_dev_blake2b512_spans over the blocks */
+  const uint64_t* att_first;        /* nblocks + 1: pz_block_gate_batch.att_first */
+  const int32_t*  block_status;     /* nblocks: what pz_block_gate_batch.block_status would have been */
+  const int32_t*  rec_status;       /* optional, natt: pz_block_gate_batch.rec_status */
+  const int32_t*  att_status;       /* natt: pz_block_gate_batch.chk.status */
+  uint64_t natt;                    /* pz_block_gate_batch.chk.natt */
+  uint8_t*  parent_ok;              /* nblocks */
+  uint8_t*  saved0;                 /* nblocks */
+  int32_t*  block_status_out;       /* nblocks: feed it to pz_block_gate_batch.block_status */
+} pz_block_parents_batch;
+/* The bytes of d_scratch (no reference counterpart). */
+uint64_t pz_block_parents_scratch_bytes(uint64_t nblocks);
+/* service.go:261-269 over a run, device pointers, on the caller's stream, asynchronous. */
+int pz_dev_block_parents(pz_block_set* set, const pz_block_parents_batch* b, void* d_scratch, void* stream);
+/* service.go:261-269 over a run, host pointers (any alignment), synchronous. */
+int pz_block_parents(pz_block_set* set, const pz_block_parents_batch* b);
+/* saveBlock (service.go:324) for the run the walk has decided: block_hash[j] becomes a key for every j
+ * with walk[j] saved or candidate (1 or 2: pz_block_walk_batch.walk); deferred blocks, at or past the
+ * walk's stop, and blocks that did not go on are untouched.  With d_flags given (pz_block_gate_batch
+ * .flags) and its bit 0 set -- the reference panics in the run -- nothing is inserted.  d_count_out
+ * (optional, one u64, 8-byte aligned) receives the set's count after the insert.  One launch of one
+ * workgroup, as pz_dev_block_set_insert.  PZ_EINVAL, before any launch: a NULL set; nblocks >= 2^31;
+ * with nblocks > 0 a NULL or misaligned d_block_hash or a NULL d_walk.  nblocks == 0 launches
+ * nothing. */
+int pz_dev_block_set_insert_walked(pz_block_set* set, const uint8_t* d_block_hash, const uint8_t* d_walk,
+                                   const uint32_t* d_flags /* optional */, uint64_t nblocks, uint64_t* d_count_out /* optional */,
+                                   void* stream);
+
 /* ---- R: ActiveState.PendingAttestations resident on the device --------------------------------
  * The attestations a block contributes (processedAttestations, blockchain/service.go:280-301)
  * become ActiveState.PendingAttestations (computeNewActiveState, core.go:223-237) and feed the

@@ -128,6 +128,20 @@ SIGNATURES = {
     "pz_block_walk_scratch_bytes": [u64, u64],
     "pz_dev_block_walk": [vp, vp, vp],
     "pz_block_walk": [vp, vp],
+    "pz_block_set_new": [vp, u64, u64, ctypes.c_int, vp],
+    "pz_block_set_free": [vp],
+    "pz_block_set_count": [vp, vp],
+    "pz_block_set_read": [vp, vp, u64, vp],
+    "pz_dev_block_set_contains": [vp, vp, u64, vp, vp],
+    "pz_block_set_contains": [vp, vp, u64, vp],
+    "pz_dev_block_set_insert": [vp, vp, vp, u64, vp],
+    "pz_block_set_insert": [vp, vp, vp, u64],
+    "pz_dev_block_set_reserve": [vp, u64, vp],
+    "pz_block_set_reserve": [vp, u64],
+    "pz_block_parents_scratch_bytes": [u64],
+    "pz_dev_block_parents": [vp, vp, vp, vp],
+    "pz_block_parents": [vp, vp],
+    "pz_dev_block_set_insert_walked": [vp, vp, vp, vp, u64, vp, vp],
     "pz_att_pool_new": [vp, ctypes.c_int, vp],
     "pz_att_pool_free": [vp],
     "pz_att_pool_scratch_bytes": [u64],
@@ -317,6 +331,15 @@ class BlockWalkBatch(ctypes.Structure):
     ]
 
 
+class BlockParentsBatch(ctypes.Structure):
+    """Mirror of ``pz_block_parents_batch`` (include/prysm_hip.h)."""
+    _fields_ = [
+        ("nblocks", u64), ("bytes", vp), ("nbytes", u64), ("bytes_beg", vp), ("bytes_len", vp), ("slot_number", vp),
+        ("block_hash", vp), ("att_first", vp), ("block_status", vp), ("rec_status", vp), ("att_status", vp), ("natt", u64),
+        ("parent_ok", vp), ("saved0", vp), ("block_status_out", vp),
+    ]
+
+
 class RecalcBatch(ctypes.Structure):
     """Mirror of ``pz_recalc_batch`` (include/prysm_hip.h)."""
     _fields_ = [
@@ -351,6 +374,7 @@ _RESTYPES = {"pz_last_error": ctypes.c_char_p, "pz_chain_free": None, "pz_set_se
              "pz_vote_cache_free": None, "pz_vote_cache_scratch_bytes": u64,
              "pz_att_pool_free": None, "pz_att_pool_scratch_bytes": u64,
              "pz_recent_hashes_free": None, "pz_block_walk_scratch_bytes": u64,
+             "pz_block_set_free": None, "pz_block_parents_scratch_bytes": u64,
              "pz_recalc_state_free": None, "pz_state_recalc_scratch_bytes": u64,
              "pz_wire_committees_bound": u64, "pz_wire_committees_scratch_bytes": u64,
              "pz_crystallized_state_bound": u64, "pz_crystallized_state_scratch_bytes": u64, "pz_active_state_bound": u64}

@@ -498,6 +498,35 @@ def walk_serialized_blocks(cache, pool, ring, data, offsets, last_justified_slot
     (the checks' statuses), ``parents_start`` (absolute: positions in the log), ``block_hash`` (n, 32)
     and, with ``want_digests``, ``msg`` (natt, 64) / ``msg_len``: zero for a row that is not PROCESSED
     or whose block is ineligible or deferred."""
+    return _walk(cache, pool, ring, None, data, offsets, last_justified_slot, last_state_recalc, shard_and_committees, balance,
+                 eligible, has_candidate, candidate_slot, lag, want_digests, device)
+
+
+def walk_serialized_blocks_saved(cache, pool, ring, saved, data, offsets, last_justified_slot, last_state_recalc,
+                                 shard_and_committees, balance, eligible=None, has_candidate=False, candidate_slot=0, lag=0,
+                                 want_digests=False, device=0):
+    """:func:`walk_serialized_blocks` with the parent check (``hasBlock(block.ParentHash())``,
+    service.go:261-269) taken on the device too, from ``saved`` (a
+    ``prysm_amd.pending.DeviceSavedBlocks``: the hashes of the blocks the DB holds,
+    ``pz_dev_block_parents``): a block's parent may be a block of the same run, which is itself saved
+    only if ITS parent was -- the device resolves that chain by pointer jumping -- and ``eligible``
+    then means CanProcessBlock alone (service.go:272, :308).  The set is first given room for its
+    count plus the run (from the count last read); the device then queues hash -> parents -> gate ->
+    walk -> insert: the hashes of the run's saved and candidate blocks before ``stop`` go into the set
+    (``pz_dev_block_set_insert_walked``; service.go:324).  Still one upload and one host read: the
+    read also brings ``parent_ok`` (uint8 per block: 0 where the reference answers "parent does not
+    exist"), which the returned dict gains, and the set's new count.  A ``ChainPanic`` leaves the set
+    as it was.  (A function of its own rather than a ``saved=`` argument: the parameter list of
+    :func:`walk_serialized_blocks` is pinned.)"""
+    if saved is None:
+        raise PzError(_lib.PZ_EINVAL, "saved is None: walk_serialized_blocks is the form without a set")
+    return _walk(cache, pool, ring, saved, data, offsets, last_justified_slot, last_state_recalc, shard_and_committees, balance,
+                 eligible, has_candidate, candidate_slot, lag, want_digests, device)
+
+
+def _walk(cache, pool, ring, saved, data, offsets, last_justified_slot, last_state_recalc, shard_and_committees, balance,
+          eligible, has_candidate, candidate_slot, lag, want_digests, device):
+    """The body of :func:`walk_serialized_blocks` (``saved`` None) and :func:`walk_serialized_blocks_saved`."""
     import torch
 
     data = np.ascontiguousarray(_lib.as_u8(data), dtype=np.uint8)
@@ -516,16 +545,37 @@ def walk_serialized_blocks(cache, pool, ring, data, offsets, last_justified_slot
         if el.numel() != n:
             raise PzError(_lib.PZ_EINVAL, "eligible holds %d entries for %d blocks" % (el.numel(), n))
         block_status = torch.where(el != 0, block_status, torch.full_like(block_status, _INELIGIBLE))
-    # one buffer, one copy: the walk's result record, the gate's flags and report, the walk's codes
-    word, report, vote_status, pend_take, flags = _gate(d, None, block_status, head=32, tail=n)
-    result, walk = word[:32].view(torch.int64), word[36 + n:]
     sh = _lib.stream_ptr(dev)
+    p = _lib.dptr
     block_hash = torch.empty((n, 32), dtype=torch.uint8, device=dev)
-    lib.call("pz_dev_blake2b512_spans", d["d_bytes"].data_ptr(), d["d_offs"][:-1].data_ptr(), d["d_offs"][1:].data_ptr(), n,
-             block_hash.data_ptr() if n else None, 32, sh)
+    hash_blocks = lambda: lib.call(  # noqa: E731
+        "pz_dev_blake2b512_spans", d["d_bytes"].data_ptr(), d["d_offs"][:-1].data_ptr(), d["d_offs"][1:].data_ptr(), n,
+        block_hash.data_ptr() if n else None, 32, sh)
+    head = 32
+    if saved is not None:
+        # hash -> parents -> gate: the parent check hands the gate a status that closes a block whose parent is not saved
+        head = 40  # (the set's new count rides behind the walk's result record)
+        saved.reserve((saved.count() if saved._count is None else saved._count) + n, device_form=True)
+        hash_blocks()
+        saved0 = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        status_out = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        parent_ok_dev = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        scratch = torch.empty(int(lib.dll.pz_block_parents_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+        pb_ = _lib.BlockParentsBatch(
+            nblocks=n, bytes=p(d["d_bytes"]), nbytes=int(offsets[-1]) if n else 0, bytes_beg=p(blk["bytes_beg"]),
+            bytes_len=p(blk["bytes_len"]), slot_number=p(blk["slot_number"]), block_hash=p(block_hash),
+            att_first=p(blk["att_first"]), block_status=p(block_status.contiguous()), rec_status=p(d["rec"]),
+            att_status=p(status.contiguous()), natt=natt, parent_ok=p(parent_ok_dev), saved0=p(saved0),
+            block_status_out=p(status_out))
+        lib.call("pz_dev_block_parents", saved._h, ctypes.byref(pb_), p(scratch), sh)
+        block_status = status_out[:n]
+    # one buffer, one copy: the walk's result record, the gate's flags and report, the walk's codes
+    word, report, vote_status, pend_take, flags = _gate(d, None, block_status, head=head, tail=n if saved is None else 2 * n)
+    result, walk = word[:32].view(torch.int64), word[head + 4 + n:head + 4 + 2 * n]
+    if saved is None:
+        hash_blocks()
     base = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
     log = torch.empty(int(lib.dll.pz_block_walk_scratch_bytes(n, natt)), dtype=torch.uint8, device=dev)
-    p = _lib.dptr
     # IsCycleTransition reads the chain's CrystallizedState AFTER updateHead (service.go:320-321, :345):
     # right after a transition block that is the new one, a cycle on, while the checks above read the old
     walk_lsr = (int(last_state_recalc) + (64 if lag else 0)) & ((1 << 64) - 1)
@@ -535,16 +585,23 @@ def walk_serialized_blocks(cache, pool, ring, data, offsets, last_justified_slot
                             vote_status=p(vote_status), pend_take=p(pend_take), parents_start=p(d["parents_start"]),
                             walk=p(walk), base=p(base), result=p(result), log=p(log), flags=p(flags))
     lib.call("pz_dev_block_walk", ring._h, ctypes.byref(b), sh)
+    if saved is not None and n:
+        word[head + 4 + 2 * n:].copy_(parent_ok_dev[:n])  # (device to device: it comes along in the one read)
+        lib.call("pz_dev_block_set_insert_walked", saved._h, p(block_hash), p(walk), p(flags), n, word[32:40].data_ptr(), sh)
     host = word.cpu().numpy()  # the one read
-    if host[32:36].view(np.uint32)[0] & 1:
+    if host[head:head + 4].view(np.uint32)[0] & 1:
         raise ChainPanic("a block of the run makes the reference panic (processAttestation or "
                          "calculateBlockVoteCache: slice bounds, core.go:353, or committee index, core.go:367)")
     if n:
         stop, ncand, has, cslot = (int(x) for x in host[:32].view(np.uint64))
     else:
         stop, ncand, has, cslot = 0, 0, int(bool(has_candidate)), int(candidate_slot) if has_candidate else 0
-    out = {"walk": host[36 + n:].copy(), "report": host[36:36 + n].copy(), "stop": stop, "ncand": ncand,
-           "has_candidate": bool(has), "candidate_slot": cslot}
+    out = {"walk": host[head + 4 + n:head + 4 + 2 * n].copy(), "report": host[head + 4:head + 4 + n].copy(), "stop": stop,
+           "ncand": ncand, "has_candidate": bool(has), "candidate_slot": cslot}
+    if saved is not None:
+        out["parent_ok"] = host[head + 4 + 2 * n:].copy()
+        if n:
+            saved._count = int(host[32:40].view(np.uint64)[0])
     if natt:
         members = np.ascontiguousarray([v for arr in shard_and_committees for e in arr for v in e[1]] or [0], dtype=np.uint32)
         cache.tally_columns(d["att"], natt, vote_status, d["committee"], d["parents_start"], log, _to_device(members, dev),

@@ -102,6 +102,88 @@ class DeviceRecentHashes(_lib.Handle):
         lib.call("pz_recent_hashes_append", self._h, _lib.ptr(rows), _lib.ptr(take), len(rows))
 
 
+class DeviceSavedBlocks(_lib.Handle):
+    """The hashes of the blocks saveBlock stored (blockchain/service.go:324, core.go:565-577) resident on
+    one device (``pz_block_set``, prysm_amd/csrc/blockparents.hip): what hasBlock (core.go:560-562)
+    answers from, so that ``blockchain.walk_serialized_blocks_saved`` resolves the parent check of
+    a whole run (service.go:261-269) on the device.  ``hashes``: the block hashes a stored DB holds
+    (byte strings or an (n, 32) uint8 array; None: none -- a chain from genesis, whose first blocks
+    have slot <= 1); ``min_keys``: room to start with (the set grows by itself, rehashing on the
+    device)."""
+    _FREE = "pz_block_set_free"
+    _STICKY = (_lib.PZ_ERANGE,)
+
+    def __init__(self, hashes=None, min_keys=1024, device=0):
+        rows = self._rows(() if hashes is None else hashes)
+        self._new("pz_block_set_new", _lib.ptr(rows), len(rows), int(min_keys), device)
+        self.device = device
+        self._count = None if len(rows) else 0  # the count as last read (None: not read yet)
+
+    @staticmethod
+    def _rows(hashes):
+        if isinstance(hashes, np.ndarray):
+            return np.ascontiguousarray(hashes, dtype=np.uint8).reshape(-1, 32)
+        hashes = [bytes(h) for h in hashes]
+        assert all(len(h) == 32 for h in hashes), "a block hash is 32 bytes"
+        return np.frombuffer(b"".join(hashes), dtype=np.uint8).reshape(-1, 32)
+
+    def count(self, strict=True):
+        """The number of distinct hashes (``pz_block_set_count``; waits for the set's last call)."""
+        n = _lib.ctypes.c_uint64(0)
+        self._rc(lib.dll.pz_block_set_count(self._h, _lib.ctypes.byref(n)), strict)
+        self._count = int(n.value)
+        return self._count
+
+    __len__ = count
+
+    def hashes(self, strict=True):
+        """Every stored hash as a byte string, in no particular order (``pz_block_set_read``)."""
+        cap = self.count(strict)
+        out = np.zeros((max(cap, 1), 32), dtype=np.uint8)
+        n = _lib.ctypes.c_uint64(0)
+        self._rc(lib.dll.pz_block_set_read(self._h, out.ctypes.data, cap, _lib.ctypes.byref(n)), strict)
+        return [out[i].tobytes() for i in range(int(n.value))]
+
+    def contains(self, hashes):
+        """hasBlock (core.go:560-562) per hash: a uint8 torch tensor for an (n, 32) uint8 device tensor
+        (current stream, asynchronous), else a numpy bool array (synchronous)."""
+        if hasattr(hashes, "data_ptr"):
+            import torch
+
+            n = hashes.numel() // 32
+            out = torch.empty(n, dtype=torch.uint8, device=hashes.device)
+            lib.call("pz_dev_block_set_contains", self._h, _lib.dptr(hashes), n, _lib.dptr(out), _lib.stream_ptr(self.device))
+            return out
+        rows = self._rows(hashes)
+        out = np.zeros(len(rows), dtype=np.uint8)
+        lib.call("pz_block_set_contains", self._h, _lib.ptr(rows), len(rows), _lib.ptr(out))
+        return out.astype(bool)
+
+    def reserve(self, min_keys, device_form=False):
+        """Room for ``min_keys`` hashes: when they need more cells every key is rehashed on the device
+        (``pz_[dev_]block_set_reserve``; ``device_form``: on the current stream, asynchronous)."""
+        if device_form:
+            lib.call("pz_dev_block_set_reserve", self._h, int(min_keys), _lib.stream_ptr(self.device))
+        else:
+            lib.call("pz_block_set_reserve", self._h, int(min_keys))
+
+    def insert(self, hashes, take=None):
+        """saveBlock's key (core.go:565-577) for the caller that decides for itself -- the transition
+        block's path: the rows with ``take[j] != 0`` (None: all) become keys, duplicates once.  An
+        (n, 32) uint8 device tensor goes in on the current stream, asynchronously, after a reserve from
+        the count last read; a numpy array or byte strings synchronously."""
+        if hasattr(hashes, "data_ptr"):
+            n = hashes.numel() // 32
+            self.reserve((self.count() if self._count is None else self._count) + n, device_form=True)
+            lib.call("pz_dev_block_set_insert", self._h, _lib.dptr(hashes), _lib.dptr(take), n, _lib.stream_ptr(self.device))
+            self._count = None
+            return
+        rows = self._rows(hashes)
+        take = None if take is None else np.ascontiguousarray(take, dtype=np.uint8)
+        lib.call("pz_block_set_insert", self._h, _lib.ptr(rows), _lib.ptr(take), len(rows))
+        self._count = None
+
+
 def recent_of(recent, recent_len=None):
     """``(rows, lens)`` on the host of what a ``recent_hashes`` argument names: a
     ``DeviceRecentHashes`` is downloaded with its stored lengths, anything else passes through."""
@@ -467,4 +549,4 @@ for _i, _name in enumerate(ResidentRecalcState._SCALARS):
     setattr(ResidentRecalcState, _name, property(lambda self, _i=_i: self.scalar(_i, strict=False)))
 
 
-__all__ = ["DevicePendingAttestations", "DeviceRecentHashes", "RecalcState", "ResidentRecalcState", "CAPS"]
+__all__ = ["DevicePendingAttestations", "DeviceRecentHashes", "DeviceSavedBlocks", "RecalcState", "ResidentRecalcState", "CAPS"]
