@@ -1025,6 +1025,84 @@ int pz_dev_block_walk(pz_recent_hashes* ring, const pz_block_walk_batch* b, void
  * of the ring's last call first.  log is optional here. */
 int pz_block_walk(pz_recent_hashes* ring, const pz_block_walk_batch* b);
 
+/* ---- T/R: a run of blocks through a cycle transition ----------------------------------------------
+ * pz_block_walk for a run that holds the transition block itself: the candidate rule and updateHead
+ * (blockchain/service.go:320-333) unchanged, and IsCycleTransition (core.go:181-183) deciding where
+ * stateRecalc (core.go:398-497, from service.go:345-353) stands in the run, not where the run ends.
+ * stateRecalc builds the CANDIDATE's states; the chain keeps its own until the next block with a
+ * larger slot promotes them (updateHead, service.go:170-227), and every block is checked and tallied
+ * against the chain's (service.go:281-318 run before :320).  CalculateRewards writes the balances in
+ * place (casper/incentives.go:22-28) on the slice stateRecalc hands on (core.go:468) and the vote
+ * cache is one shared map (core.go:494-496), so the two pairs of states differ in two host scalars,
+ * the ring's history entry, and the side of stateRecalc a tally or a pool append falls on.
+ *
+ * go, pending, cand_j, rank_j (the candidates before j) and the log as pz_block_walk_batch defines
+ * them; last_state_recalc is the value IsCycleTransition reads for the first candidate, as there.
+ *   T = with lag == 0 the first candidate with slot >= last_state_recalc + 64; it is INCLUDED.
+ *   L = with lag == 0 the first candidate after T, tested against last_state_recalc + 128 (the sums
+ *       wrap as Go's uint64); with lag == 1 the first candidate, tested against last_state_recalc.
+ *   lag == 0: L no transition: stop = L + 1, lag_out = 0; L a transition (a slot jump of a cycle or
+ *       more): stop = L (deferred: one stateRecalc a call), lag_out = 1; the run ends before an L:
+ *       stop = nblocks, lag_out = 1; no T: stop = nblocks, lag_out = 0.
+ *   lag == 1: L no transition: stop = L + 1, lag_out = 0; L a transition: it is taken as T, stop =
+ *       L + 1, lag_out = 1; no L: stop = nblocks, lag_out = 1.
+ *   walk[j] as pz_block_walk_batch.walk (the same four codes: pz_dev_block_set_insert_walked takes
+ *       them unchanged); base[j] = 1 - lagged_j + rank_j with lagged_j = lag or j > T, 0 for a
+ *       deferred block: a lagged block reads the ring as it was before T's hash went in.
+ * Per row i of block b = att_block[i]: parents_start[i] += base[b];
+ *   vote0[i] = vote_status[i] where b <= T (no T: every b) and b < stop -- the rows calculateBlockVoteCache
+ *              tallies BEFORE stateRecalc, T's own included (service.go:313-318 precede :345);
+ *   vote1[i] = vote_status[i] where T < b < stop -- the rows tallied after it, against the balances
+ *              CalculateRewards left; elsewhere a PZ_ATT_PROCESSED becomes PZ_ATT_NOT_PROCESSED;
+ *   take0[i] = pend_take[i] (NULL: 1) and walk[b] == 2 and b < T (no T: every b): what the chain's
+ *              PendingAttestations holds when stateRecalc reads and prunes it;
+ *   take1[i] = pend_take[i] and walk[b] == 2 and b >= T: what computeNewActiveState appends to the
+ *              new ActiveState (core.go:223-237), T's own rows first.
+ * No row names a log position at or past 129 + rank_b (blockcycle_dev.h has the proof), so `log`
+ * with n_recent = 129 + nblocks is `recent` for both tallies and the message digests.  The promoted
+ * ActiveState's RecentBlockHashes -- stateRecalc's `recent` (core.go:413), 128 entries -- starts at log
+ * entry 1 + t_rank.  The ring rolls as in pz_block_walk (flags likewise).
+ * result[8]: stop, the candidates before stop (T and L included), has_candidate / candidate_slot
+ * after block stop - 1, t_index (all ones: no T), t_rank, t_slot (0 without a T), lag_out.
+ *
+ * Three dependent launches on the caller's stream (scan, rows, and the walk's roll: DESIGN.md §3); no
+ * workgroup waits for another, the host reads nothing.  PZ_EINVAL, before any launch: a NULL ring or
+ * batch; nblocks >= 2^31; lag > 1; with nblocks > 0 a NULL slot_number, report, block_hash, walk,
+ * base, result or (device form) log, a block_hash or log that is not 16-byte aligned; with natt > 0
+ * a NULL att_block, vote_status, parents_start, vote0, vote1, take0 or take1.  nblocks == 0 launches
+ * nothing and leaves the ring as it is. */
+typedef struct pz_block_cycle_batch {   /* every member a pointer or a uint64_t */
+  uint64_t nblocks;
+  const uint64_t* slot_number;   /* nblocks: pz_block_cols_out.slot_number */
+  const uint8_t*  report;        /* nblocks: pz_block_gate_batch.report */
+  const uint8_t*  block_hash;    /* nblocks x 32: Block.Hash(), pz_dev_blake2b512_spans over the blocks */
+  uint64_t has_candidate, candidate_slot;   /* carried in: candidateBlock != nilBlock, its SlotNumber */
+  uint64_t last_state_recalc;    /* as pz_block_walk_batch.last_state_recalc: with lag, the new state's */
+  uint64_t lag;                  /* 1: the last call's lag_out: a transition block's states are not promoted yet */
+  uint64_t natt;
+  const uint32_t* att_block;     /* natt: pz_block_cols_out.att_block */
+  const int32_t*  vote_status;   /* natt: pz_block_gate_batch.vote_status */
+  const uint8_t*  pend_take;     /* optional, natt: pz_block_gate_batch.pend_take */
+  uint64_t* parents_start;       /* natt: pz_att_check_batch.parents_start, made absolute in place */
+  int32_t*  vote0;               /* natt: the tally's status before stateRecalc */
+  int32_t*  vote1;               /* natt: the tally's status after it */
+  uint8_t*  take0;               /* natt: the pool's take before stateRecalc */
+  uint8_t*  take1;               /* natt: the pool's take after it */
+  uint8_t*  walk;                /* nblocks */
+  uint64_t* base;                /* nblocks */
+  uint64_t* result;              /* 8 */
+  uint8_t*  log;                 /* pz_block_cycle_scratch_bytes(nblocks, natt) bytes: (129 + nblocks) x 32 */
+  const uint32_t* flags;         /* optional: pz_block_gate_batch.flags; with bit 0 set the ring stays as it is */
+} pz_block_cycle_batch;
+/* The bytes of `log` (no reference counterpart). */
+uint64_t pz_block_cycle_scratch_bytes(uint64_t nblocks, uint64_t natt);
+/* service.go:320-361 over a run with its transition block, device pointers, on the caller's stream,
+ * asynchronous. */
+int pz_dev_block_cycle(pz_recent_hashes* ring, const pz_block_cycle_batch* b, void* stream);
+/* service.go:320-361 over a run with its transition block, host pointers (any alignment),
+ * synchronous; waits for the stream of the ring's last call first.  log is optional here. */
+int pz_block_cycle(pz_recent_hashes* ring, const pz_block_cycle_batch* b);
+
 /* ---- R: the saved-block set resident on the device, and the parent check over a run ---------------
  * hasBlock (blockchain/core.go:560-562) answers blockProcessing's first question about a received
  * block, `hasBlock(block.ParentHash())` (service.go:261-269), from the blocks saveBlock stored

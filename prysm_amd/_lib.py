@@ -128,6 +128,9 @@ SIGNATURES = {
     "pz_block_walk_scratch_bytes": [u64, u64],
     "pz_dev_block_walk": [vp, vp, vp],
     "pz_block_walk": [vp, vp],
+    "pz_block_cycle_scratch_bytes": [u64, u64],
+    "pz_dev_block_cycle": [vp, vp, vp],
+    "pz_block_cycle": [vp, vp],
     "pz_block_set_new": [vp, u64, u64, ctypes.c_int, vp],
     "pz_block_set_free": [vp],
     "pz_block_set_count": [vp, vp],
@@ -331,6 +334,16 @@ class BlockWalkBatch(ctypes.Structure):
     ]
 
 
+class BlockCycleBatch(ctypes.Structure):
+    """Mirror of ``pz_block_cycle_batch`` (include/prysm_hip.h)."""
+    _fields_ = [
+        ("nblocks", u64), ("slot_number", vp), ("report", vp), ("block_hash", vp), ("has_candidate", u64),
+        ("candidate_slot", u64), ("last_state_recalc", u64), ("lag", u64), ("natt", u64), ("att_block", vp),
+        ("vote_status", vp), ("pend_take", vp), ("parents_start", vp), ("vote0", vp), ("vote1", vp), ("take0", vp),
+        ("take1", vp), ("walk", vp), ("base", vp), ("result", vp), ("log", vp), ("flags", vp),
+    ]
+
+
 class BlockParentsBatch(ctypes.Structure):
     """Mirror of ``pz_block_parents_batch`` (include/prysm_hip.h)."""
     _fields_ = [
@@ -374,6 +387,7 @@ _RESTYPES = {"pz_last_error": ctypes.c_char_p, "pz_chain_free": None, "pz_set_se
              "pz_vote_cache_free": None, "pz_vote_cache_scratch_bytes": u64,
              "pz_att_pool_free": None, "pz_att_pool_scratch_bytes": u64,
              "pz_recent_hashes_free": None, "pz_block_walk_scratch_bytes": u64,
+             "pz_block_cycle_scratch_bytes": u64,
              "pz_block_set_free": None, "pz_block_parents_scratch_bytes": u64,
              "pz_recalc_state_free": None, "pz_state_recalc_scratch_bytes": u64,
              "pz_wire_committees_bound": u64, "pz_wire_committees_scratch_bytes": u64,

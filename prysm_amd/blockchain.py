@@ -19,6 +19,11 @@ heavy work, batched per call:
      instance on the HBM-resident validator arrays.
 
 Where the reference panics, ``ChainPanic`` is raised and the chain object is spent.
+
+The ``*_serialized_blocks`` functions and ``ResidentChain`` are the same pipeline composed from the
+device-resident objects of ``prysm_amd.votes`` and ``prysm_amd.pending`` instead of the engine:
+``ResidentChain.process_serialized`` takes a run of received blocks, its cycle transition included,
+with one upload and one host read (``pz_dev_block_cycle``, prysm_amd/csrc/blockcycle.hip).
 """
 import ctypes
 import warnings
@@ -113,12 +118,20 @@ def _split_decode_check(payload, offsets, last_justified_slot, last_state_recalc
     import torch
 
     dev = torch.device("cuda", device)
-    n = len(offsets) - 1
-    d_bytes, d_offs = _to_device(payload, dev), _to_device(offsets, dev)
+    table = [_to_device(a, dev) for a in _committee_table(shard_and_committees)]
+    return _decode_check(_to_device(payload, dev), _to_device(offsets, dev), len(offsets) - 1, last_justified_slot,
+                         last_state_recalc, n_recent, len(shard_and_committees), table, dev, want_committee)
+
+
+def _decode_check(d_bytes, d_offs, n, last_justified_slot, last_state_recalc, n_recent, narr, table, dev, want_committee):
+    """:func:`_split_decode_check` from the device on: ``d_bytes`` / ``d_offs`` are the uploaded bytes
+    and offsets, ``table`` the committee table's four device tensors (``_committee_table``'s order)
+    over ``narr`` slots."""
+    import torch
+
     blk = wire.unwire_blocks_device(d_bytes, d_offs, n)
     natt = int(blk["natt"].item())
     att = wire.unwire_attestations_device(d_bytes, blk["att_beg"], blk["att_end"], natt, 0)
-    table = [_to_device(a, dev) for a in _committee_table(shard_and_committees)]
     status = torch.zeros(max(natt, 1), dtype=torch.int32, device=dev)
     comm = torch.zeros(max(natt, 1), dtype=torch.int32, device=dev) if want_committee else None
     pstart = torch.zeros(max(natt, 1), dtype=torch.int64, device=dev)
@@ -126,7 +139,7 @@ def _split_decode_check(payload, offsets, last_justified_slot, last_state_recalc
         natt, att["slot"].data_ptr(), att["justified_slot"].data_ptr(), att["shard_id"].data_ptr(),
         att["n_oblique"].data_ptr(), att["attester_bitfield"].data_ptr(), att["attester_bitfield_offs"].data_ptr(),
         blk["att_block_slot"].data_ptr(), last_justified_slot, last_state_recalc, n_recent,
-        len(shard_and_committees), *[t.data_ptr() for t in table], status.data_ptr(),
+        narr, *[t.data_ptr() for t in table], status.data_ptr(),
         comm.data_ptr() if want_committee else None, pstart.data_ptr(), att["last_byte"].data_ptr())
     lib.call("pz_dev_check_attestations", ctypes.byref(b), _lib.stream_ptr(dev))
     rec = att["status"][:natt]
@@ -555,20 +568,8 @@ def _walk(cache, pool, ring, saved, data, offsets, last_justified_slot, last_sta
     if saved is not None:
         # hash -> parents -> gate: the parent check hands the gate a status that closes a block whose parent is not saved
         head = 40  # (the set's new count rides behind the walk's result record)
-        saved.reserve((saved.count() if saved._count is None else saved._count) + n, device_form=True)
         hash_blocks()
-        saved0 = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        status_out = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        parent_ok_dev = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        scratch = torch.empty(int(lib.dll.pz_block_parents_scratch_bytes(n)), dtype=torch.uint8, device=dev)
-        pb_ = _lib.BlockParentsBatch(
-            nblocks=n, bytes=p(d["d_bytes"]), nbytes=int(offsets[-1]) if n else 0, bytes_beg=p(blk["bytes_beg"]),
-            bytes_len=p(blk["bytes_len"]), slot_number=p(blk["slot_number"]), block_hash=p(block_hash),
-            att_first=p(blk["att_first"]), block_status=p(block_status.contiguous()), rec_status=p(d["rec"]),
-            att_status=p(status.contiguous()), natt=natt, parent_ok=p(parent_ok_dev), saved0=p(saved0),
-            block_status_out=p(status_out))
-        lib.call("pz_dev_block_parents", saved._h, ctypes.byref(pb_), p(scratch), sh)
-        block_status = status_out[:n]
+        block_status, parent_ok_dev = _parents(saved, d, int(offsets[-1]) if n else 0, block_status, block_hash)
     # one buffer, one copy: the walk's result record, the gate's flags and report, the walk's codes
     word, report, vote_status, pend_take, flags = _gate(d, None, block_status, head=head, tail=n if saved is None else 2 * n)
     result, walk = word[:32].view(torch.int64), word[head + 4 + n:head + 4 + 2 * n]
@@ -603,10 +604,49 @@ def _walk(cache, pool, ring, saved, data, offsets, last_justified_slot, last_sta
         if n:
             saved._count = int(host[32:40].view(np.uint64)[0])
     if natt:
-        members = np.ascontiguousarray([v for arr in shard_and_committees for e in arr for v in e[1]] or [0], dtype=np.uint32)
-        cache.tally_columns(d["att"], natt, vote_status, d["committee"], d["parents_start"], log, _to_device(members, dev),
-                            d["table"][3], _to_device(np.ascontiguousarray(balance, dtype=np.uint64), dev))
+        cache.tally_columns(d["att"], natt, vote_status, d["committee"], d["parents_start"], log,
+                            _to_device(_members(shard_and_committees), dev), d["table"][3],
+                            _to_device(np.ascontiguousarray(balance, dtype=np.uint64), dev))
         pool.append_columns(d["att"], natt, status.contiguous(), d["committee"], take=pend_take)
+    return _run_outputs(out, d, walk, block_status, block_hash, log, want_digests)
+
+
+def _members(shard_and_committees):
+    """Every committee's members in table order: the tally's ``members`` beside ``_committee_table``'s coffs."""
+    return np.ascontiguousarray([v for arr in shard_and_committees for e in arr for v in e[1]] or [0], dtype=np.uint32)
+
+
+def _parents(saved, d, nbytes, block_status, block_hash):
+    """The parent check of a run on the current stream, behind Block.Hash: room in ``saved`` for its
+    count plus the run, then ``pz_dev_block_parents`` over :func:`_decode_check`'s tensors ``d``.
+    Returns ``(block_status_out, parent_ok)`` device tensors: the gate's ``block_status``, which
+    closes a block whose parent is not saved, and one byte per block."""
+    import torch
+
+    dev, n, natt, blk = d["dev"], d["n"], d["natt"], d["blk"]
+    p = _lib.dptr
+    saved.reserve((saved.count() if saved._count is None else saved._count) + n, device_form=True)
+    saved0 = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    status_out = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    parent_ok = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    scratch = torch.empty(int(lib.dll.pz_block_parents_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+    b = _lib.BlockParentsBatch(
+        nblocks=n, bytes=p(d["d_bytes"]), nbytes=nbytes, bytes_beg=p(blk["bytes_beg"]),
+        bytes_len=p(blk["bytes_len"]), slot_number=p(blk["slot_number"]), block_hash=p(block_hash),
+        att_first=p(blk["att_first"]), block_status=p(block_status.contiguous()), rec_status=p(d["rec"]),
+        att_status=p(d["status"].contiguous()), natt=natt, parent_ok=p(parent_ok), saved0=p(saved0),
+        block_status_out=p(status_out))
+    lib.call("pz_dev_block_parents", saved._h, ctypes.byref(b), p(scratch), _lib.stream_ptr(dev))
+    return status_out[:n], parent_ok
+
+
+def _run_outputs(out, d, walk, block_status, block_hash, log, want_digests):
+    """What a walked run returns per row and per block, added to ``out``: with ``want_digests`` the
+    message digests over the log (zero for a row that is not PROCESSED or whose block is ineligible
+    or deferred), then ``att_first``, ``att_status``, ``parents_start`` and ``block_hash``."""
+    import torch
+
+    n, natt, blk, status = d["n"], d["natt"], d["blk"], d["status"]
     if want_digests:
         if natt:
             att_block = blk["att_block"][:natt].long()
@@ -720,8 +760,6 @@ def state_recalc_resident(pool, cache, state, recent_hashes, block_slot):
     block's SlotNumber.  Computes what ``state_recalc_device`` computes and raises ``ChainPanic`` where it does; a
     pending ShardBlockHash longer than the state's ``hash_stride`` is refused whole (PZ_ERANGE).
     Returns the winners (one attestation row per record, 0xFFFFFFFF: none)."""
-    import torch
-
     from prysm_amd.pending import DeviceRecentHashes
 
     dev = state.balance.device
@@ -730,6 +768,15 @@ def state_recalc_resident(pool, cache, state, recent_hashes, block_slot):
     else:
         recent = _recent_array(recent_hashes)
         d_recent, n_recent = _to_device(recent if len(recent) else np.zeros((1, 32), np.uint8), dev), len(recent)
+    return _recalc_resident(pool, cache, state, d_recent, n_recent, block_slot)["winner"]
+
+
+def _recalc_resident(pool, cache, state, d_recent, n_recent, block_slot):
+    """``pz_dev_state_recalc`` with ``d_recent`` (a uint8 device tensor, read where it lies) as
+    RecentBlockHashes(), then the handle's one read: ``ResidentRecalcState.read()``'s dict."""
+    import torch
+
+    dev = state.balance.device
     b = _lib.RecalcBatch(nval=state.nval, balance=state.balance.data_ptr(), start=state.start.data_ptr(),
                          end=state.end.data_ptr(), members=state.members.data_ptr(), coffs=state.coffs.data_ptr(),
                          recent=d_recent.data_ptr(), n_recent=n_recent, block_slot=int(block_slot))
@@ -743,7 +790,7 @@ def state_recalc_resident(pool, cache, state, recent_hashes, block_slot):
     if rc != _lib.PZ_OK:
         raise _lib.PzError(rc, msg)
     try:
-        return state.winners()
+        return state.read()
     except _lib.PzError as e:
         if e.code == _lib.PZ_EINDEX:
             raise ChainPanic(str(e)) from None
@@ -760,6 +807,224 @@ def resident_state_roots(pool, state, recent_hashes, field12, recent_len=None, c
     the remaining arguments: as ``ResidentRecalcState.wire``."""
     return (pool.active_state_root(recent_hashes, recent_len),
             state.root(field12, crosslinking_start_shard, dynasty_seed, dynasty_seed_last_reset))
+
+
+_NO_T = (1 << 64) - 1  # pz_block_cycle_batch.result's t_index without a transition block
+
+
+class ResidentChain:
+    """blockProcessing (blockchain/service.go:229-363) over the resident objects, transition blocks
+    included: ``cache`` (a ``prysm_amd.votes.DeviceVoteCache``), ``pool`` (a
+    ``prysm_amd.pending.DevicePendingAttestations``), ``ring`` (a ``DeviceRecentHashes``), ``saved`` (a
+    ``DeviceSavedBlocks``) and ``state`` (a ``ResidentRecalcState``), with ``shard_and_committees`` =
+    ShardAndCommitteesForSlots, which stateRecalc hands on unchanged (core.go:469): its device form is
+    built here, once.  The balances are ``state.balance``, read where they lie by both tallies.
+
+    The object keeps the host side of the carry between calls: ``has_candidate`` /
+    ``candidate_slot`` (candidateBlock), ``lag`` (1: the pending candidate is a transition block, so
+    its states are not the chain's yet) and, while ``lag`` is set, the chain's own
+    ``(last_justified_slot, last_state_recalc)`` beside the candidate's, which are the state
+    handle's.  That pair and the ring's history entry are all that tells the two pairs of states
+    apart: CalculateRewards writes the balances in place (casper/incentives.go:22-28) on the slice
+    stateRecalc hands to the new state (core.go:468), so the chain's old CrystallizedState tallies
+    with the rewarded balances from the transition block on."""
+
+    def __init__(self, cache, pool, ring, saved, state, shard_and_committees, device=0):
+        import torch
+
+        self.cache, self.pool, self.ring, self.saved, self.state = cache, pool, ring, saved, state
+        self.device = device
+        dev = torch.device("cuda", device)
+        self._narr = len(shard_and_committees)
+        self._table = [_to_device(a, dev) for a in _committee_table(shard_and_committees)]
+        self._members = _to_device(_members(shard_and_committees), dev)
+        self.has_candidate, self.candidate_slot, self.lag = False, 0, 0
+        scal = state.read()["scalars"]
+        self._cand = (int(scal[2]), int(scal[0]))  # (last_justified_slot, last_state_recalc) of the state handle
+        self._chain = None                         # the chain's own pair while lag is set
+        self.calls = 0      # submissions so far: one upload and one read each
+        self.resubmits = 0  # of them, runs submitted again without the blocks past their stop
+        self.spent = False  # a call failed after its host read: the objects no longer match the carry
+
+    RUN_BLOCKS = 1024  # process_all's submission: the scan's tile, and far more than a cycle's blocks of one chain
+
+    def chain_scalars(self):
+        """``(last_justified_slot, last_state_recalc)`` of the chain's CrystallizedState: what a
+        received block is checked against (service.go:281-301)."""
+        return self._chain if self.lag else self._cand
+
+    def process_serialized(self, data, offsets, eligible=None, want_digests=False):
+        """A run of consecutive received blocks held as bytes, in ONE call, the run's cycle transition
+        included.  One upload (offsets, ``eligible`` and bytes in one buffer); then the device queues
+        split, decode, the checks with the chain's scalars, Block.Hash, the parent check against
+        ``saved``, the gate, ``pz_dev_block_cycle`` and the insert of the walked hashes; then the one
+        host read, as :func:`walk_serialized_blocks_saved` makes it.  After it: the tally and the pool
+        append of the rows before stateRecalc; with a transition block T in the run
+        ``pz_dev_state_recalc`` over the promoted ActiveState's window (log entry ``1 + t_rank``) at
+        T's slot; then the tally and the append of the rows after it, against the same balance
+        pointer.  The read and the recalc's own are the only waits.
+
+        ``eligible``: CanProcessBlock alone (service.go:272, :308), one 0/1 per block (None: all).
+        The run ends behind the block that promotes T's states (or before it, if that block is a
+        transition too): blocks at or past ``stop`` are untouched, submit them again
+        (:meth:`process_all`).
+
+        Where the reference panics on a row of a block BEFORE ``stop`` ``ChainPanic`` is raised and
+        nothing lands.  The checks and the gate run over every block of the upload before the scan
+        knows ``stop``, and the gate's one panic bit covers them all; but a block at or past ``stop``
+        is not processed by this call, and it was checked against scalars that may be cycles behind
+        the ones the reference will check it with (a row's committee index ``slot -
+        last_state_recalc`` leaves the table then, core.go:367, without any panic in the reference).
+        So when the bit is set and ``stop`` cuts the run, nothing of the first submission has landed
+        (the ring, the set, cache and pool are as they were) and the blocks before ``stop`` are
+        submitted again alone: a second upload and read, on this path only.  The scan's decisions for a
+        block depend on the blocks before it alone, so that submission stops where the first did and
+        its bit speaks of the run's own blocks; the outputs returned are the first submission's,
+        which cover every block of the call.
+
+        Where stateRecalc itself panics ``ChainPanic`` is raised with the rows before it landed, the
+        ring rolled and the set grown -- the reference too tallies and saves before it panics
+        (service.go:313-324 precede :345) -- and nothing after it.  After that, or after any other
+        error raised behind the host read (a pool or cache capacity, a ShardBlockHash longer than
+        the state's ``hash_stride``), the objects no longer match the carry: the object is spent and
+        every later call raises.
+
+        Returns :func:`walk_serialized_blocks_saved`'s dict plus ``t_index`` (the transition
+        block's index, None: none) and ``lag`` (the lag carried out)."""
+        if self.spent:
+            raise ChainPanic("an earlier call failed behind its host read: the object is spent")
+        data = np.ascontiguousarray(_lib.as_u8(data), dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        if eligible is not None:
+            eligible = np.ascontiguousarray(eligible, dtype=np.uint8)
+            if eligible.size != n:
+                raise PzError(_lib.PZ_EINVAL, "eligible holds %d entries for %d blocks" % (eligible.size, n))
+        out, panic = self._submit(data, offsets, eligible, want_digests)
+        if panic and out["stop"] < n:
+            stop = out["stop"]
+            self.resubmits += 1
+            head, panic = self._submit(data, offsets[:stop + 1], None if eligible is None else eligible[:stop], False)
+            if not panic and (head["stop"], head["ncand"], head["t_index"], head["lag"]) != \
+                    (stop, out["ncand"], out["t_index"], out["lag"]):
+                self.spent = True
+                raise PzError(_lib.PZ_EINVAL, "a run submitted again without its deferred blocks stopped elsewhere")
+        if panic:
+            raise ChainPanic("a block of the run makes the reference panic (processAttestation or "
+                             "calculateBlockVoteCache: slice bounds, core.go:353, or committee index, core.go:367)")
+        return out
+
+    def _submit(self, data, offsets, eligible, want_digests):
+        """One upload, the device queue, one read, and -- unless the gate's panic bit is set -- the
+        landing.  Returns ``(out, panic)``; with ``panic`` nothing has landed and the carry is as it was."""
+        import torch
+
+        cache, pool, ring, saved, state = self.cache, self.pool, self.ring, self.saved, self.state
+        n = len(offsets) - 1
+        nbytes = int(offsets[-1]) if n else 0
+        dev = torch.device("cuda", self.device)
+        # the one upload: offsets | eligible | bytes (the span hash reads whole dwords: 4 bytes of slack)
+        o_end = 8 * (n + 1)
+        e_end = o_end + n
+        b_beg = e_end + (-e_end) % 16
+        host = np.zeros(b_beg + nbytes + 4, dtype=np.uint8)
+        host[:o_end] = offsets.view(np.uint8)
+        host[o_end:e_end] = 1 if eligible is None else eligible != 0
+        host[b_beg:b_beg + nbytes] = data[:nbytes]
+        up = _to_device(host, dev)
+        d_offs, el, d_bytes = up[:o_end].view(torch.int64), up[o_end:e_end], up[b_beg:]
+        self.calls += 1
+
+        lag = int(self.lag)
+        ljs, lsr = self.chain_scalars()
+        d = _decode_check(d_bytes, d_offs, n, ljs, lsr, 128, self._narr, self._table, dev, want_committee=True)
+        natt, blk, status = d["natt"], d["blk"], d["status"]
+        block_status = torch.where(el != 0, blk["status"], torch.full_like(blk["status"], _INELIGIBLE))
+        sh = _lib.stream_ptr(dev)
+        p = _lib.dptr
+        block_hash = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+        lib.call("pz_dev_blake2b512_spans", d_bytes.data_ptr(), d_offs[:-1].data_ptr(), d_offs[1:].data_ptr(), n,
+                 block_hash.data_ptr() if n else None, 32, sh)
+        block_status, parent_ok_dev = _parents(saved, d, nbytes, block_status, block_hash)
+        # one buffer, one copy: the cycle's result record, the set's count, the gate's flags and report,
+        # the walk codes, parent_ok
+        head = 72
+        word, report, vote_status, pend_take, flags = _gate(d, None, block_status, head=head, tail=2 * n)
+        result, walk = word[:64].view(torch.int64), word[head + 4 + n:head + 4 + 2 * n]
+        base = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        log = torch.empty(int(lib.dll.pz_block_cycle_scratch_bytes(n, natt)), dtype=torch.uint8, device=dev)
+        vote = torch.empty((2, max(natt, 1)), dtype=torch.int32, device=dev)
+        take = torch.empty((2, max(natt, 1)), dtype=torch.uint8, device=dev)
+        # IsCycleTransition reads the state the first candidate promotes (service.go:320-321, :345):
+        # the state handle's, which with lag is a cycle ahead of the scalars the checks read
+        b = _lib.BlockCycleBatch(nblocks=n, slot_number=p(blk["slot_number"]), report=p(report), block_hash=p(block_hash),
+                                 has_candidate=int(bool(self.has_candidate)), candidate_slot=int(self.candidate_slot),
+                                 last_state_recalc=self._cand[1], lag=lag, natt=natt, att_block=p(blk["att_block"]),
+                                 vote_status=p(vote_status), pend_take=p(pend_take), parents_start=p(d["parents_start"]),
+                                 vote0=vote[0].data_ptr(), vote1=vote[1].data_ptr(), take0=take[0].data_ptr(),
+                                 take1=take[1].data_ptr(), walk=p(walk), base=p(base), result=p(result), log=p(log),
+                                 flags=p(flags))
+        lib.call("pz_dev_block_cycle", ring._h, ctypes.byref(b), sh)
+        if n:
+            word[head + 4 + 2 * n:].copy_(parent_ok_dev[:n])  # (device to device: it comes along in the one read)
+            lib.call("pz_dev_block_set_insert_walked", saved._h, p(block_hash), p(walk), p(flags), n, word[64:72].data_ptr(), sh)
+        host = word.cpu().numpy()  # the one read
+        panic = bool(host[head:head + 4].view(np.uint32)[0] & 1)  # (then nothing rolled and nothing was inserted)
+        if n:
+            stop, ncand, has, cslot, t_index, t_rank, t_slot, lag_out = (int(x) for x in host[:64].view(np.uint64))
+            if not panic:
+                saved._count = int(host[64:72].view(np.uint64)[0])
+        else:
+            stop, ncand, has, cslot = 0, 0, int(bool(self.has_candidate)), int(self.candidate_slot) if self.has_candidate else 0
+            t_index, t_rank, t_slot, lag_out = _NO_T, 0, 0, lag
+        out = {"walk": host[head + 4 + n:head + 4 + 2 * n].copy(), "report": host[head + 4:head + 4 + n].copy(), "stop": stop,
+               "ncand": ncand, "has_candidate": bool(has), "candidate_slot": cslot, "parent_ok": host[head + 4 + 2 * n:].copy(),
+               "t_index": None if t_index == _NO_T else t_index, "lag": lag_out}
+
+        def land(phase):  # calculateBlockVoteCache and processedAttestations of one side of stateRecalc
+            cache.tally_columns(d["att"], natt, vote[phase], d["committee"], d["parents_start"], log, self._members,
+                                self._table[3], state.balance)
+            pool.append_columns(d["att"], natt, status.contiguous(), d["committee"], take=take[phase])
+
+        if not panic:
+            try:  # from here on the ring has rolled and the set has grown: an error leaves the objects ahead of the carry
+                if natt:
+                    land(0)
+                chain_pair = self._chain
+                if t_index != _NO_T:
+                    window = log[32 * (1 + t_rank):32 * (1 + t_rank + 128)]  # the promoted ActiveState's RecentBlockHashes
+                    pre = self._cand
+                    scal = _recalc_resident(pool, cache, state, window, 128, t_slot)["scalars"]
+                    self._cand = (int(scal[2]), int(scal[0]))
+                    chain_pair = pre  # what the chain keeps until T's states are promoted
+                    if natt:
+                        land(1)
+            except BaseException:
+                self.spent = True
+                raise
+            self.has_candidate, self.candidate_slot, self.lag = bool(has), cslot, lag_out
+            self._chain = chain_pair if lag_out else None
+        return _run_outputs(out, d, walk, block_status, block_hash, log, want_digests), panic
+
+    def process_all(self, data, offsets, eligible=None, want_digests=False):
+        """:meth:`process_serialized` from ``stop`` on until the bytes are used up: a list of its
+        dicts in call order, each with ``start`` (the index of its first block in ``offsets``).  A
+        submission holds at most ``RUN_BLOCKS`` blocks, so that a long chain is not uploaded and
+        decoded whole once per cycle."""
+        data = np.ascontiguousarray(_lib.as_u8(data), dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        outs, i = [], 0
+        while i < n:
+            hi = min(n, i + self.RUN_BLOCKS)
+            out = self.process_serialized(data[int(offsets[i]):int(offsets[hi])], offsets[i:hi + 1] - offsets[i],
+                                          None if eligible is None else eligible[i:hi], want_digests)
+            if out["stop"] == 0:  # (a run of one block or more always takes its first)
+                raise PzError(_lib.PZ_EINVAL, "the run at block %d took nothing" % i)
+            out["start"] = i
+            outs.append(out)
+            i += out["stop"]
+        return outs
 
 
 def serialize_blocks(blocks):

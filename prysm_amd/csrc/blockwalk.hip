@@ -239,17 +239,14 @@ int check_walk(const pz_recent_hashes* h, const pz_block_walk_batch* b, bool dev
 }
 
 hipError_t launch_walk(pz_recent_hashes* h, const pz_block_walk_batch& b, hipStream_t s, Events* ev = nullptr) {
-  const RingSet from = set_of(h, h->live), to = set_of(h, h->live ^ 1);
+  const RingSet from = set_of(h, h->live);
   stamp(ev, 0, s);
   hipLaunchKernelGGL(pz_block_walk_scan_kernel, dim3(1), dim3(kBwThreads), 0, s, b, from);
   stamp(ev, 1, s);
   if (b.natt) hipLaunchKernelGGL(pz_block_walk_rows_kernel, dim3((uint32_t)((b.natt + kRowThreads - 1) / kRowThreads)), dim3(kRowThreads), 0, s, b);
   stamp(ev, 2, s);
-  hipLaunchKernelGGL(pz_block_walk_roll_kernel, dim3(1), dim3(kRollThreads), 0, s, (const uint8_t*)b.log, (const uint64_t*)b.result,
-                     b.flags, b.nblocks, from, to);
+  const hipError_t e = recent_hashes_roll(h, b.log, b.result, b.flags, b.nblocks, s);
   stamp(ev, 3, s);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) h->live ^= 1, h->last = s;
   return e;
 }
 
@@ -269,6 +266,20 @@ int check_append(const pz_recent_hashes* h, const uint8_t* hashes, uint64_t n) {
 }
 
 }  // namespace
+
+// What blockcycle.hip takes from the ring (resident.h): the live set to scan from, and the walk's
+// own roll launch with its swap.  The caller holds the handle's lock.
+Resident* resident_of(pz_recent_hashes* h) { return h; }
+const uint8_t* recent_hashes_live(pz_recent_hashes* h) { return set_of(h, h->live).hashes; }
+hipError_t recent_hashes_roll(pz_recent_hashes* h, const uint8_t* log, const uint64_t* result, const uint32_t* flags, uint64_t nblocks,
+                              hipStream_t s) {
+  hipLaunchKernelGGL(pz_block_walk_roll_kernel, dim3(1), dim3(kRollThreads), 0, s, log, result, flags, nblocks, set_of(h, h->live),
+                     set_of(h, h->live ^ 1));
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) h->live ^= 1, h->last = s;
+  return e;
+}
+
 }  // namespace pz
 
 using namespace pz;

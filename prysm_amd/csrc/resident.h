@@ -67,6 +67,15 @@ struct HostForm {
 // (wire_state.hip); defined beside each struct.
 Resident* resident_of(pz_att_pool* h);
 Resident* resident_of(pz_recalc_state* h);
+Resident* resident_of(pz_recent_hashes* h);
+
+// The recent-hashes ring for a launch sequence written outside its file (blockcycle.hip), under the
+// handle's lock: the live set's 129 x 32 bytes, and the walk's roll (blockwalk.hip) -- the other set
+// becomes log entries [ncand, ncand + 129) with ncand = result[1], unless bit 0 of *flags is set --
+// after which the sets are swapped and s is the stream the ring's reads wait for.
+const uint8_t* recent_hashes_live(pz_recent_hashes* h);
+hipError_t recent_hashes_roll(pz_recent_hashes* h, const uint8_t* log, const uint64_t* result, const uint32_t* flags, uint64_t nblocks,
+                              hipStream_t s);
 
 // The vote cache's lookup side: device pointers, valid for the handle's lifetime.
 struct VcView {
