@@ -444,10 +444,8 @@ def tally_serialized_blocks(cache, data, offsets, last_justified_slot, last_stat
             raise ChainPanic("a block of the batch makes the reference panic (processAttestation or "
                              "calculateBlockVoteCache: slice bounds, core.go:353, or committee index, core.go:367)")
         if natt:
-            members = np.ascontiguousarray([v for arr in shard_and_committees for e in arr for v in e[1]] or [0],
-                                           dtype=np.uint32)
             cache.tally_columns(d["att"], natt, vote_status, d["committee"], d["parents_start"], _to_device(recent, dev),
-                                _to_device(members, dev), d["table"][3],
+                                _to_device(_members(shard_and_committees), dev), d["table"][3],
                                 _to_device(np.ascontiguousarray(balance, dtype=np.uint64), dev))
             if pending is not None:
                 pending.append_columns(d["att"], natt, status.contiguous(), d["committee"], take=pend_take)
@@ -456,11 +454,9 @@ def tally_serialized_blocks(cache, data, offsets, last_justified_slot, last_stat
         open_, att_block, count, nproc = _open_blocks(d)
         report = open_.long() * (BLOCK_TALLIED + (BLOCK_MIXED - BLOCK_TALLIED) * (nproc != count).long())
         take = (report == BLOCK_TALLIED)[att_block].to(torch.uint8)
-        members = np.ascontiguousarray([v for arr in shard_and_committees for e in arr for v in e[1]] or [0],
-                                       dtype=np.uint32)
         coffs = _committee_table(shard_and_committees)[3]
         cache.tally_columns(d["att"], natt, status.contiguous(), d["committee"], d["parents_start"],
-                            _to_device(recent, dev), _to_device(members, dev), _to_device(coffs, dev),
+                            _to_device(recent, dev), _to_device(_members(shard_and_committees), dev), _to_device(coffs, dev),
                             _to_device(np.ascontiguousarray(balance, dtype=np.uint64), dev), take=take)
         if pending is not None:
             _pend(pending, d, candidate)
@@ -551,64 +547,106 @@ def _walk(cache, pool, ring, saved, data, offsets, last_justified_slot, last_sta
     payload = np.concatenate([data[:int(offsets[-1])] if n else data[:0], np.zeros(4, np.uint8)])
     d = _split_decode_check(payload, offsets, last_justified_slot, last_state_recalc, 128, shard_and_committees, device,
                             want_committee=True)
-    dev, natt, blk, status = d["dev"], d["natt"], d["blk"], d["status"]
-    block_status = blk["status"]
+    dev, natt, blk = d["dev"], d["natt"], d["blk"]
+    el = None
     if eligible is not None:
         el = _to_device(np.ascontiguousarray(eligible, dtype=np.uint8), dev)
         if el.numel() != n:
             raise PzError(_lib.PZ_EINVAL, "eligible holds %d entries for %d blocks" % (el.numel(), n))
-        block_status = torch.where(el != 0, block_status, torch.full_like(block_status, _INELIGIBLE))
-    sh = _lib.stream_ptr(dev)
+    q = _queue_run(d, int(offsets[-1]) if n else 0, _fold_eligible(blk["status"], el), saved, 4)
     p = _lib.dptr
-    block_hash = torch.empty((n, 32), dtype=torch.uint8, device=dev)
-    hash_blocks = lambda: lib.call(  # noqa: E731
-        "pz_dev_blake2b512_spans", d["d_bytes"].data_ptr(), d["d_offs"][:-1].data_ptr(), d["d_offs"][1:].data_ptr(), n,
-        block_hash.data_ptr() if n else None, 32, sh)
-    head = 32
-    if saved is not None:
-        # hash -> parents -> gate: the parent check hands the gate a status that closes a block whose parent is not saved
-        head = 40  # (the set's new count rides behind the walk's result record)
-        hash_blocks()
-        block_status, parent_ok_dev = _parents(saved, d, int(offsets[-1]) if n else 0, block_status, block_hash)
-    # one buffer, one copy: the walk's result record, the gate's flags and report, the walk's codes
-    word, report, vote_status, pend_take, flags = _gate(d, None, block_status, head=head, tail=n if saved is None else 2 * n)
-    result, walk = word[:32].view(torch.int64), word[head + 4 + n:head + 4 + 2 * n]
-    if saved is None:
-        hash_blocks()
     base = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
     log = torch.empty(int(lib.dll.pz_block_walk_scratch_bytes(n, natt)), dtype=torch.uint8, device=dev)
     # IsCycleTransition reads the chain's CrystallizedState AFTER updateHead (service.go:320-321, :345):
     # right after a transition block that is the new one, a cycle on, while the checks above read the old
     walk_lsr = (int(last_state_recalc) + (64 if lag else 0)) & ((1 << 64) - 1)
-    b = _lib.BlockWalkBatch(nblocks=n, slot_number=p(blk["slot_number"]), report=p(report), block_hash=p(block_hash),
+    b = _lib.BlockWalkBatch(nblocks=n, slot_number=p(blk["slot_number"]), report=p(q["report"]), block_hash=p(q["block_hash"]),
                             has_candidate=int(bool(has_candidate)), candidate_slot=int(candidate_slot),
                             last_state_recalc=walk_lsr, lag=int(lag), natt=natt, att_block=p(blk["att_block"]),
-                            vote_status=p(vote_status), pend_take=p(pend_take), parents_start=p(d["parents_start"]),
-                            walk=p(walk), base=p(base), result=p(result), log=p(log), flags=p(flags))
-    lib.call("pz_dev_block_walk", ring._h, ctypes.byref(b), sh)
-    if saved is not None and n:
-        word[head + 4 + 2 * n:].copy_(parent_ok_dev[:n])  # (device to device: it comes along in the one read)
-        lib.call("pz_dev_block_set_insert_walked", saved._h, p(block_hash), p(walk), p(flags), n, word[32:40].data_ptr(), sh)
-    host = word.cpu().numpy()  # the one read
-    if host[head:head + 4].view(np.uint32)[0] & 1:
-        raise ChainPanic("a block of the run makes the reference panic (processAttestation or "
-                         "calculateBlockVoteCache: slice bounds, core.go:353, or committee index, core.go:367)")
-    if n:
-        stop, ncand, has, cslot = (int(x) for x in host[:32].view(np.uint64))
-    else:
-        stop, ncand, has, cslot = 0, 0, int(bool(has_candidate)), int(candidate_slot) if has_candidate else 0
-    out = {"walk": host[head + 4 + n:head + 4 + 2 * n].copy(), "report": host[head + 4:head + 4 + n].copy(), "stop": stop,
-           "ncand": ncand, "has_candidate": bool(has), "candidate_slot": cslot}
-    if saved is not None:
-        out["parent_ok"] = host[head + 4 + 2 * n:].copy()
-        if n:
-            saved._count = int(host[32:40].view(np.uint64)[0])
+                            vote_status=p(q["vote_status"]), pend_take=p(q["pend_take"]), parents_start=p(d["parents_start"]),
+                            walk=p(q["walk"]), base=p(base), result=p(q["result"]), log=p(log), flags=p(q["flags"]))
+    lib.call("pz_dev_block_walk", ring._h, ctypes.byref(b), q["sh"])
+    _, panic, out = _read_run(q, d, saved, (0, 0, int(bool(has_candidate)), int(candidate_slot) if has_candidate else 0))
+    if panic:
+        raise ChainPanic(_RUN_PANIC)
     if natt:
-        cache.tally_columns(d["att"], natt, vote_status, d["committee"], d["parents_start"], log,
+        cache.tally_columns(d["att"], natt, q["vote_status"], d["committee"], d["parents_start"], log,
                             _to_device(_members(shard_and_committees), dev), d["table"][3],
                             _to_device(np.ascontiguousarray(balance, dtype=np.uint64), dev))
-        pool.append_columns(d["att"], natt, status.contiguous(), d["committee"], take=pend_take)
-    return _run_outputs(out, d, walk, block_status, block_hash, log, want_digests)
+        pool.append_columns(d["att"], natt, d["status"].contiguous(), d["committee"], take=q["pend_take"])
+    return _run_outputs(out, d, q["walk"], q["block_status"], q["block_hash"], log, want_digests)
+
+
+_RUN_PANIC = ("a block of the run makes the reference panic (processAttestation or "
+              "calculateBlockVoteCache: slice bounds, core.go:353, or committee index, core.go:367)")
+
+
+def _fold_eligible(block_status, el):
+    """The gate's block status with ``el`` (a uint8 device tensor, one 0/1 per block; None: all)
+    folded in: an ineligible block gets a status that is not PZ_OK, which closes it."""
+    import torch
+
+    return block_status if el is None else torch.where(el != 0, block_status, torch.full_like(block_status, _INELIGIBLE))
+
+
+def _queue_run(d, nbytes, block_status, saved, result_words):
+    """What a walked run queues before its scan, on the current stream, over :func:`_decode_check`'s
+    tensors ``d`` (``nbytes`` of block bytes) and the folded ``block_status``: with ``saved`` (a
+    ``DeviceSavedBlocks``, else None) Block.Hash, the parent check, which hands the gate a status
+    that closes a block whose parent is not saved, and the gate; without it the gate, then
+    Block.Hash.  It allocates the one read-back buffer, ``result | set count | flags | report | walk |
+    parent_ok`` (``result_words``: the scan's result record; the count and ``parent_ok`` only with a
+    set).  Returns a dict of device tensors: ``word`` (the buffer) with its views ``result``,
+    ``flags``, ``report`` and ``walk``, ``block_hash``, the ``block_status`` the gate took,
+    ``parent_ok`` (None without a set), ``vote_status`` and ``pend_take``; ``at``, the byte offset
+    each part of the buffer starts at; and ``sh``, the stream."""
+    import torch
+
+    dev, n = d["dev"], d["n"]
+    sh = _lib.stream_ptr(dev)
+    block_hash = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    hash_blocks = lambda: lib.call(  # noqa: E731
+        "pz_dev_blake2b512_spans", d["d_bytes"].data_ptr(), d["d_offs"][:-1].data_ptr(), d["d_offs"][1:].data_ptr(), n,
+        block_hash.data_ptr() if n else None, 32, sh)
+    parent_ok = None
+    if saved is not None:
+        hash_blocks()
+        block_status, parent_ok = _parents(saved, d, nbytes, block_status, block_hash)
+    at = {"count": 8 * result_words}
+    at["flags"] = at["count"] + (8 if saved is not None else 0)
+    at["report"] = at["flags"] + 4
+    at["walk"] = at["report"] + n
+    at["parent_ok"] = at["walk"] + n
+    word, report, vote_status, pend_take, flags = _gate(d, None, block_status, head=at["flags"], tail=n if saved is None else 2 * n)
+    if saved is None:
+        hash_blocks()
+    return {"at": at, "sh": sh, "word": word, "result": word[:at["count"]].view(torch.int64), "flags": flags, "report": report,
+            "walk": word[at["walk"]:at["parent_ok"]], "block_hash": block_hash, "block_status": block_status,
+            "parent_ok": parent_ok, "vote_status": vote_status, "pend_take": pend_take}
+
+
+def _read_run(q, d, saved, empty):
+    """Behind the scan of :func:`_queue_run`'s ``q``: with ``saved``, ``parent_ok`` into the buffer
+    (device to device: it comes along) and the walked hashes into the set, which leaves its new
+    count there (``pz_dev_block_set_insert_walked``; service.go:324); then the ONE host read.
+    Returns ``(record, panic, out)``: the scan's result record as ints (``empty`` for a run of no
+    block, which launches nothing), the gate's panic bit -- with it nothing rolled and nothing was
+    inserted -- and the dict a walked run returns, so far."""
+    n, at, word = d["n"], q["at"], q["word"]
+    if saved is not None and n:
+        word[at["parent_ok"]:].copy_(q["parent_ok"][:n])
+        lib.call("pz_dev_block_set_insert_walked", saved._h, _lib.dptr(q["block_hash"]), _lib.dptr(q["walk"]), _lib.dptr(q["flags"]),
+                 n, word[at["count"]:].data_ptr(), q["sh"])
+    host = word.cpu().numpy()  # the one read
+    panic = bool(host[at["flags"]:at["report"]].view(np.uint32)[0] & 1)
+    record = tuple(int(x) for x in host[:at["count"]].view(np.uint64)) if n else tuple(empty)
+    if saved is not None and n and not panic:
+        saved._count = int(host[at["count"]:at["flags"]].view(np.uint64)[0])
+    out = {"walk": host[at["walk"]:at["parent_ok"]].copy(), "report": host[at["report"]:at["walk"]].copy(), "stop": record[0],
+           "ncand": record[1], "has_candidate": bool(record[2]), "candidate_slot": record[3]}
+    if saved is not None:
+        out["parent_ok"] = host[at["parent_ok"]:].copy()
+    return record, panic, out
 
 
 def _members(shard_and_committees):
@@ -910,8 +948,7 @@ class ResidentChain:
                 self.spent = True
                 raise PzError(_lib.PZ_EINVAL, "a run submitted again without its deferred blocks stopped elsewhere")
         if panic:
-            raise ChainPanic("a block of the run makes the reference panic (processAttestation or "
-                             "calculateBlockVoteCache: slice bounds, core.go:353, or committee index, core.go:367)")
+            raise ChainPanic(_RUN_PANIC)
         return out
 
     def _submit(self, data, offsets, eligible, want_digests):
@@ -939,47 +976,25 @@ class ResidentChain:
         ljs, lsr = self.chain_scalars()
         d = _decode_check(d_bytes, d_offs, n, ljs, lsr, 128, self._narr, self._table, dev, want_committee=True)
         natt, blk, status = d["natt"], d["blk"], d["status"]
-        block_status = torch.where(el != 0, blk["status"], torch.full_like(blk["status"], _INELIGIBLE))
-        sh = _lib.stream_ptr(dev)
+        q = _queue_run(d, nbytes, _fold_eligible(blk["status"], el), saved, 8)
         p = _lib.dptr
-        block_hash = torch.empty((n, 32), dtype=torch.uint8, device=dev)
-        lib.call("pz_dev_blake2b512_spans", d_bytes.data_ptr(), d_offs[:-1].data_ptr(), d_offs[1:].data_ptr(), n,
-                 block_hash.data_ptr() if n else None, 32, sh)
-        block_status, parent_ok_dev = _parents(saved, d, nbytes, block_status, block_hash)
-        # one buffer, one copy: the cycle's result record, the set's count, the gate's flags and report,
-        # the walk codes, parent_ok
-        head = 72
-        word, report, vote_status, pend_take, flags = _gate(d, None, block_status, head=head, tail=2 * n)
-        result, walk = word[:64].view(torch.int64), word[head + 4 + n:head + 4 + 2 * n]
         base = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
         log = torch.empty(int(lib.dll.pz_block_cycle_scratch_bytes(n, natt)), dtype=torch.uint8, device=dev)
         vote = torch.empty((2, max(natt, 1)), dtype=torch.int32, device=dev)
         take = torch.empty((2, max(natt, 1)), dtype=torch.uint8, device=dev)
         # IsCycleTransition reads the state the first candidate promotes (service.go:320-321, :345):
         # the state handle's, which with lag is a cycle ahead of the scalars the checks read
-        b = _lib.BlockCycleBatch(nblocks=n, slot_number=p(blk["slot_number"]), report=p(report), block_hash=p(block_hash),
+        b = _lib.BlockCycleBatch(nblocks=n, slot_number=p(blk["slot_number"]), report=p(q["report"]), block_hash=p(q["block_hash"]),
                                  has_candidate=int(bool(self.has_candidate)), candidate_slot=int(self.candidate_slot),
                                  last_state_recalc=self._cand[1], lag=lag, natt=natt, att_block=p(blk["att_block"]),
-                                 vote_status=p(vote_status), pend_take=p(pend_take), parents_start=p(d["parents_start"]),
+                                 vote_status=p(q["vote_status"]), pend_take=p(q["pend_take"]), parents_start=p(d["parents_start"]),
                                  vote0=vote[0].data_ptr(), vote1=vote[1].data_ptr(), take0=take[0].data_ptr(),
-                                 take1=take[1].data_ptr(), walk=p(walk), base=p(base), result=p(result), log=p(log),
-                                 flags=p(flags))
-        lib.call("pz_dev_block_cycle", ring._h, ctypes.byref(b), sh)
-        if n:
-            word[head + 4 + 2 * n:].copy_(parent_ok_dev[:n])  # (device to device: it comes along in the one read)
-            lib.call("pz_dev_block_set_insert_walked", saved._h, p(block_hash), p(walk), p(flags), n, word[64:72].data_ptr(), sh)
-        host = word.cpu().numpy()  # the one read
-        panic = bool(host[head:head + 4].view(np.uint32)[0] & 1)  # (then nothing rolled and nothing was inserted)
-        if n:
-            stop, ncand, has, cslot, t_index, t_rank, t_slot, lag_out = (int(x) for x in host[:64].view(np.uint64))
-            if not panic:
-                saved._count = int(host[64:72].view(np.uint64)[0])
-        else:
-            stop, ncand, has, cslot = 0, 0, int(bool(self.has_candidate)), int(self.candidate_slot) if self.has_candidate else 0
-            t_index, t_rank, t_slot, lag_out = _NO_T, 0, 0, lag
-        out = {"walk": host[head + 4 + n:head + 4 + 2 * n].copy(), "report": host[head + 4:head + 4 + n].copy(), "stop": stop,
-               "ncand": ncand, "has_candidate": bool(has), "candidate_slot": cslot, "parent_ok": host[head + 4 + 2 * n:].copy(),
-               "t_index": None if t_index == _NO_T else t_index, "lag": lag_out}
+                                 take1=take[1].data_ptr(), walk=p(q["walk"]), base=p(base), result=p(q["result"]), log=p(log),
+                                 flags=p(q["flags"]))
+        lib.call("pz_dev_block_cycle", ring._h, ctypes.byref(b), q["sh"])
+        empty = (0, 0, int(bool(self.has_candidate)), int(self.candidate_slot) if self.has_candidate else 0, _NO_T, 0, 0, lag)
+        (_, _, has, cslot, t_index, t_rank, t_slot, lag_out), panic, out = _read_run(q, d, saved, empty)
+        out["t_index"], out["lag"] = None if t_index == _NO_T else t_index, lag_out
 
         def land(phase):  # calculateBlockVoteCache and processedAttestations of one side of stateRecalc
             cache.tally_columns(d["att"], natt, vote[phase], d["committee"], d["parents_start"], log, self._members,
@@ -1004,7 +1019,7 @@ class ResidentChain:
                 raise
             self.has_candidate, self.candidate_slot, self.lag = bool(has), cslot, lag_out
             self._chain = chain_pair if lag_out else None
-        return _run_outputs(out, d, walk, block_status, block_hash, log, want_digests), panic
+        return _run_outputs(out, d, q["walk"], q["block_status"], q["block_hash"], log, want_digests), panic
 
     def process_all(self, data, offsets, eligible=None, want_digests=False):
         """:meth:`process_serialized` from ``stop`` on until the bytes are used up: a list of its

@@ -52,7 +52,6 @@ namespace pz {
 
 // pz_block_cycle_batch.result: the walk's four words, then T and the lag to carry.
 enum { kBcTIndex = kBwResultWords, kBcTRank, kBcTSlot, kBcLagOut, kBcResultWords };
-constexpr uint32_t kBcTile = 1024, kBcWaves = kBcTile / 64;  // the scan's tile: a ballot word a wave
 
 // What IsCycleTransition reads for L (core.go:181-183 on the promoted state).
 PZ_HD uint64_t bc_lsr_after(uint64_t last_state_recalc, uint64_t lag) {
@@ -78,16 +77,6 @@ PZ_HD void bc_candidate(BcState& s, uint64_t j, uint64_t slot, uint64_t last_sta
   s.stop = lag || !tr ? j + 1 : j;
 }
 
-// The first set bit at or after tile lane `from` of a tile's ballot words (kBcTile: none).
-PZ_HD uint32_t bc_first(const uint64_t* ballot, uint32_t from) {
-  for (uint32_t k = from >> 6; k < kBcWaves; ++k) {
-    uint64_t m = ballot[k];
-    if (k == from >> 6) m &= ~uint64_t(0) << (from & 63);
-    if (m) return 64 * k + (uint32_t)__builtin_ctzll(m);
-  }
-  return kBcTile;
-}
-
 // The same rule a tile at a time, from the tile's ballots: cand (the candidates), tr (the candidates
 // with bw_transition(slot, last_state_recalc)) and tr_after (those with bw_transition(slot,
 // bc_lsr_after)).  tests/blockcycle_san.cpp holds it against bc_candidate block by block.
@@ -95,12 +84,12 @@ PZ_HD void bc_tile(BcState& s, uint64_t t0, uint64_t lag, const uint64_t* cand, 
   if (s.stop != kBwNone) return;
   uint32_t from = 0;
   if (!lag && s.t_index == kBwNone) {
-    const uint32_t t = bc_first(tr, 0);
-    if (t == kBcTile) return;
+    const uint32_t t = bw_first(tr, 0);
+    if (t == kBwTile) return;
     s.t_index = t0 + t, s.lag_out = 1, from = t + 1;
   }
-  const uint32_t l = bc_first(cand, from);
-  if (l == kBcTile) return;
+  const uint32_t l = bw_first(cand, from);
+  if (l == kBwTile) return;
   const bool after = (tr_after[l >> 6] >> (l & 63)) & 1;
   s.l_index = t0 + l, s.lag_out = after;
   if (lag && after) s.t_index = s.l_index;

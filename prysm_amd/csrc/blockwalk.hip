@@ -8,11 +8,15 @@
 // pz_dev_block_walk is three dependent launches on the caller's stream; no workgroup waits for
 // another and the host reads nothing:
 //   scan  ONE workgroup of 1,024 lanes, a lane per block, tiles of 1,024 blocks taken in sequence
-//         with the carry (pending, max slot, candidates so far, stop) in registers, identical in
-//         every lane.  Per tile: a wave max-scan by __shfl_up and a __ballot for "a block went on
-//         before me", the waves' sums through LDS (two barriers a tile).  It copies the ring into the
-//         head of the log, writes walk / base, the candidates' hashes behind the ring (two 16-byte
-//         loads and stores each), zeroes the log's unused tail and leaves the result record.
+//         with the carry (BwCarry: pending, max slot, candidates so far) and the stop in registers,
+//         identical in every lane.  Per tile: the shared round 1 (blockscan_wave.h: a wave max-scan by
+//         __shfl_up and a __ballot for "a block went on before me", the waves' words through LDS,
+//         bw_round1), then two ballot words a wave in LDS -- the candidates, and the candidates
+//         under bw_transition -- from which every lane takes its rank (bw_rank) and the tile's stop
+//         (bw_tile_stop); two barriers a tile.  It copies the ring into the head of the log, writes
+//         walk / base, the candidates' hashes behind the ring (two 16-byte loads and stores each),
+//         zeroes the log's unused tail and leaves the result record.  The cycle's scan
+//         (blockcycle.hip) is the same round with its own ballots, state rule and record.
 //   rows  a lane per attestation row: parents_start made absolute, pend_take and vote_status
 //         narrowed by the row's block.
 //   roll  the ring's other buffer set = the last 129 entries of the log; ncand is read from the
@@ -22,7 +26,7 @@
 
 #include <cstring>
 
-#include "blockwalk_dev.h"
+#include "blockscan_wave.h"
 #include "resident.h"
 
 struct pz_recent_hashes : pz::Resident {
@@ -37,7 +41,6 @@ struct pz_recent_hashes : pz::Resident {
 namespace pz {
 namespace {
 
-constexpr int kBwThreads = 1024, kBwWaves = kBwThreads / 64;
 constexpr int kRollThreads = 320;                    // >= 258: a lane per 16-byte piece of the ring
 constexpr uint32_t kRingPieces = 2 * (uint32_t)kBwRing;
 constexpr size_t kRingBytes = kBwRing * 32, kLenBytes = 144;
@@ -48,35 +51,17 @@ struct RingSet {
   uint8_t* lens;
 };
 
-__device__ __forceinline__ void copy32(uint8_t* dst, const uint8_t* src) {  // both 16-byte aligned
-  const uint4 a = reinterpret_cast<const uint4*>(src)[0], b = reinterpret_cast<const uint4*>(src)[1];
-  reinterpret_cast<uint4*>(dst)[0] = a;
-  reinterpret_cast<uint4*>(dst)[1] = b;
-}
-
-// Inclusive max-scan over the wave.
-__device__ __forceinline__ uint64_t wmaxscan(uint64_t x) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t y = __shfl_up(x, d, 64);
-    if (lane >= d && y > x) x = y;
-  }
-  return x;
-}
-
-extern "C" __global__ void __launch_bounds__(kBwThreads) pz_block_walk_scan_kernel(pz_block_walk_batch g, RingSet ring) {
-  __shared__ uint64_t s_max[kBwWaves], s_fslot[kBwWaves], s_fin[3];
-  __shared__ uint32_t s_fgo[kBwWaves], s_cnt[kBwWaves], s_fcand[kBwWaves], s_ftr[kBwWaves];
+extern "C" __global__ void __launch_bounds__(kBwTile) pz_block_walk_scan_kernel(pz_block_walk_batch g, RingSet ring) {
+  __shared__ ScanWords s_r1;
+  __shared__ uint64_t s_cb[kBwWaves], s_tb[kBwWaves], s_fin[3];
   const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const uint64_t n = g.nblocks, lag = g.lag;
-  if (tid < kRingPieces) reinterpret_cast<uint4*>(g.log)[tid] = reinterpret_cast<const uint4*>(ring.hashes)[tid];
+  scan_ring_head(g.log, ring.hashes);
 
-  // the carry: the same values in every lane
-  bool c_pending = g.has_candidate != 0;
-  uint64_t c_max = c_pending ? g.candidate_slot : 0, c_cnt = 0, c_stop = kBwNone;
+  BwCarry c = bw_carry(g.has_candidate, g.candidate_slot);  // the same values in every lane
+  uint64_t c_stop = kBwNone;
   bool fin_in_lds = false;
-  for (uint64_t t0 = 0; t0 < n; t0 += kBwThreads) {
+  for (uint64_t t0 = 0; t0 < n; t0 += kBwTile) {
     const uint64_t j = t0 + tid;
     const bool in = j < n;
     if (c_stop != kBwNone) {  // past the stop: left for the caller to submit again
@@ -86,70 +71,33 @@ extern "C" __global__ void __launch_bounds__(kBwThreads) pz_block_walk_scan_kern
     const bool go = in && bw_go(g.report[j]);
     const uint64_t slot = in ? g.slot_number[j] : 0;
     // ---- round 1: the largest slot before me, and whether anything is pending before me ----
-    const uint64_t inc = wmaxscan(bw_scan_value(go, true, slot));
-    uint64_t before = __shfl_up(inc, 1, 64);
-    if (lane == 0) before = 0;
-    const uint64_t gob = __ballot(go);
-    const uint32_t fl = gob ? (uint32_t)__builtin_ctzll(gob) : 64;
-    const uint64_t fs = __shfl(slot, (int)(fl & 63), 64);
-    if (lane == 63) s_max[w] = inc;
-    if (lane == 0) s_fgo[w] = fl, s_fslot[w] = fs;
-    __syncthreads();
-    uint64_t tile_max = c_max, first = kBwNone, fslot = 0;
-    if (c_max > before) before = c_max;
-    for (int k = 0; k < kBwWaves; ++k) {
-      const uint64_t m = s_max[k];
-      if (k < (int)w && m > before) before = m;
-      if (m > tile_max) tile_max = m;
-      if (!c_pending && first == kBwNone && s_fgo[k] < 64) first = t0 + 64 * k + s_fgo[k], fslot = s_fslot[k];
-    }
-    // with nothing carried in, the first block that goes on is the candidate whatever its slot
-    const bool pending = c_pending || first < j;  // (kBwNone < j never holds)
-    if (first < j && fslot > before) before = fslot;
-    if (first != kBwNone && bw_scan_value(true, false, fslot) > tile_max) tile_max = fslot;
-    const bool cand = bw_candidate(go, pending, slot, before);
+    const BwRound1 r = scan_round1(s_r1, c, t0, j, go, slot);
     // ---- round 2: the candidates before me, and the stop ----
-    const uint64_t cb = __ballot(cand), tb = __ballot(cand && bw_transition(slot, g.last_state_recalc));
-    if (lane == 0) {
-      s_cnt[w] = (uint32_t)__builtin_popcountll(cb);
-      s_fcand[w] = cb ? (uint32_t)__builtin_ctzll(cb) : 64;
-      s_ftr[w] = tb ? (uint32_t)__builtin_ctzll(tb) : 64;
-    }
+    const uint64_t cb = __ballot(r.cand), tb = __ballot(r.cand && bw_transition(slot, g.last_state_recalc));
+    if (lane == 0) s_cb[w] = cb, s_tb[w] = tb;
     __syncthreads();
-    uint64_t rank = c_cnt + (uint64_t)__builtin_popcountll(cb & ((1ull << lane) - 1));
-    uint64_t tile_cnt = 0, fcand = kBwNone, ftr = kBwNone;
-    for (int k = 0; k < kBwWaves; ++k) {
-      if (k < (int)w) rank += s_cnt[k];
-      tile_cnt += s_cnt[k];
-      if (fcand == kBwNone && s_fcand[k] < 64) fcand = t0 + 64 * k + s_fcand[k];
-      if (ftr == kBwNone && s_ftr[k] < 64) ftr = t0 + 64 * k + s_ftr[k];
-    }
-    // (the tile's smallest bw_stop_at: its first transition candidate, or with lag one past the
-    // run's first candidate)
-    uint64_t stop = ftr;
-    if (lag && c_cnt == 0 && fcand != kBwNone && fcand + 1 < stop) stop = fcand + 1;
-    if (stop >= n) stop = kBwNone;
+    const BwRank k = bw_rank(c, s_cb, tid);
+    const uint64_t stop = bw_tile_stop(c, t0, lag, n, s_cb, s_tb);
     const bool deferred = j >= stop;
     if (in) {
-      g.walk[j] = bw_walk(go, cand, deferred);
-      g.base[j] = bw_base(lag, rank, deferred);
-      if (cand && !deferred) copy32(g.log + 32 * (kBwRing + rank), g.block_hash + 32 * j);
+      g.walk[j] = bw_walk(go, r.cand, deferred);
+      g.base[j] = bw_base(lag, k.rank, deferred);
+      if (r.cand && !deferred) scan_put_hash(g.log, k.rank, g.block_hash, j);
     }
-    if (in && j == stop) s_fin[0] = rank, s_fin[1] = pending, s_fin[2] = before;  // the state before the stop
-    if (stop != kBwNone && stop < t0 + kBwThreads) fin_in_lds = true;
+    if (in && j == stop) s_fin[0] = k.rank, s_fin[1] = r.pending, s_fin[2] = r.before;  // the state before the stop
+    if (stop != kBwNone && stop < t0 + kBwTile) fin_in_lds = true;  // (one past lane 1,023: the carry is that state)
     c_stop = stop;
-    c_cnt += tile_cnt, c_max = tile_max, c_pending = c_pending || first != kBwNone;
+    bw_advance(c, r, k.tile_cnt);
   }
   __syncthreads();
-  const uint64_t ncand = fin_in_lds ? s_fin[0] : c_cnt;
+  const uint64_t ncand = fin_in_lds ? s_fin[0] : c.cnt;
   if (tid == 0) {
     g.result[kBwStop] = c_stop == kBwNone ? n : c_stop;
     g.result[kBwNcand] = ncand;
-    g.result[kBwHasCandidate] = fin_in_lds ? s_fin[1] : (uint64_t)c_pending;
-    g.result[kBwCandidateSlot] = fin_in_lds ? s_fin[2] : c_max;
+    g.result[kBwHasCandidate] = fin_in_lds ? s_fin[1] : (uint64_t)c.pending;
+    g.result[kBwCandidateSlot] = fin_in_lds ? s_fin[2] : c.max;
   }
-  uint4* log16 = reinterpret_cast<uint4*>(g.log);
-  for (uint64_t p = 2 * (kBwRing + ncand) + tid; p < 2 * (kBwRing + n); p += kBwThreads) log16[p] = make_uint4(0, 0, 0, 0);
+  scan_zero_tail(g.log, ncand, n);
 }
 
 extern "C" __global__ void __launch_bounds__(kRowThreads) pz_block_walk_rows_kernel(pz_block_walk_batch g) {
@@ -176,20 +124,20 @@ extern "C" __global__ void __launch_bounds__(kRollThreads) pz_block_walk_roll_ke
 }
 
 // computeNewActiveState's append (core.go:230-232) for n hashes of which take (NULL: all) chooses.
-extern "C" __global__ void __launch_bounds__(kBwThreads) pz_recent_append_kernel(const uint8_t* hashes, const uint8_t* take, uint64_t n,
+extern "C" __global__ void __launch_bounds__(kBwTile) pz_recent_append_kernel(const uint8_t* hashes, const uint8_t* take, uint64_t n,
                                                                                  RingSet from, RingSet to) {
   __shared__ uint64_t s_tot[kBwWaves];
   __shared__ uint32_t s_cnt[kBwWaves];
   const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   uint64_t mine = 0;  // this wave's taken
-  for (uint64_t t0 = 0; t0 < n; t0 += kBwThreads) {
+  for (uint64_t t0 = 0; t0 < n; t0 += kBwTile) {
     const uint64_t j = t0 + tid;
     mine += (uint64_t)__builtin_popcountll(__ballot(j < n && (!take || take[j])));
   }
   if (lane == 0) s_tot[w] = mine;
   __syncthreads();
   uint64_t total = 0;
-  for (int k = 0; k < kBwWaves; ++k) total += s_tot[k];
+  for (int k = 0; k < (int)kBwWaves; ++k) total += s_tot[k];
   if (tid < kRingPieces) {  // what stays of the old ring
     const uint64_t k = tid >> 1;
     if (k >= total) {
@@ -198,14 +146,14 @@ extern "C" __global__ void __launch_bounds__(kBwThreads) pz_recent_append_kernel
     }
   }
   uint64_t c = 0;
-  for (uint64_t t0 = 0; t0 < n; t0 += kBwThreads) {
+  for (uint64_t t0 = 0; t0 < n; t0 += kBwTile) {
     const uint64_t j = t0 + tid;
     const bool t = j < n && (!take || take[j]);
     const uint64_t tb = __ballot(t);
     if (lane == 0) s_cnt[w] = (uint32_t)__builtin_popcountll(tb);
     __syncthreads();
     uint64_t rank = c + (uint64_t)__builtin_popcountll(tb & ((1ull << lane) - 1));
-    for (int k = 0; k < kBwWaves; ++k) {
+    for (int k = 0; k < (int)kBwWaves; ++k) {
       if (k < (int)w) rank += s_cnt[k];
       c += s_cnt[k];
     }
@@ -224,24 +172,10 @@ RingSet set_of(pz_recent_hashes* h, int which) {
 
 int check_ring(const pz_recent_hashes* h) { return h ? PZ_OK : fail(PZ_EINVAL, "the recent-hashes handle is null"); }
 
-// 1: nothing to launch.
-int check_walk(const pz_recent_hashes* h, const pz_block_walk_batch* b, bool device_form) {
-  if (!h || !b) return fail(PZ_EINVAL, "block walk: null handle or batch");
-  if (b->nblocks >= (1ull << 31)) return fail(PZ_EINVAL, "nblocks %llu: 2^31 blocks or more", (unsigned long long)b->nblocks);
-  if (b->lag > 1) return fail(PZ_EINVAL, "lag %llu: 0 or 1", (unsigned long long)b->lag);
-  if (b->nblocks == 0) return 1;
-  if (!b->slot_number || !b->report || !b->block_hash || !b->walk || !b->base || !b->result)
-    return fail(PZ_EINVAL, "block walk: null slot_number / report / block_hash / walk / base / result");
-  if (device_form && !b->log) return fail(PZ_EINVAL, "block walk: null log");
-  if (b->natt && (!b->att_block || !b->vote_status || !b->parents_start))
-    return fail(PZ_EINVAL, "block walk: null att_block / vote_status / parents_start");
-  return PZ_OK;
-}
-
-hipError_t launch_walk(pz_recent_hashes* h, const pz_block_walk_batch& b, hipStream_t s, Events* ev = nullptr) {
+hipError_t launch_walk(pz_recent_hashes* h, const pz_block_walk_batch& b, hipStream_t s, Events* ev) {
   const RingSet from = set_of(h, h->live);
   stamp(ev, 0, s);
-  hipLaunchKernelGGL(pz_block_walk_scan_kernel, dim3(1), dim3(kBwThreads), 0, s, b, from);
+  hipLaunchKernelGGL(pz_block_walk_scan_kernel, dim3(1), dim3(kBwTile), 0, s, b, from);
   stamp(ev, 1, s);
   if (b.natt) hipLaunchKernelGGL(pz_block_walk_rows_kernel, dim3((uint32_t)((b.natt + kRowThreads - 1) / kRowThreads)), dim3(kRowThreads), 0, s, b);
   stamp(ev, 2, s);
@@ -251,7 +185,7 @@ hipError_t launch_walk(pz_recent_hashes* h, const pz_block_walk_batch& b, hipStr
 }
 
 hipError_t launch_append(pz_recent_hashes* h, const uint8_t* d_hashes, const uint8_t* d_take, uint64_t n, hipStream_t s) {
-  hipLaunchKernelGGL(pz_recent_append_kernel, dim3(1), dim3(kBwThreads), 0, s, d_hashes, d_take, n, set_of(h, h->live),
+  hipLaunchKernelGGL(pz_recent_append_kernel, dim3(1), dim3(kBwTile), 0, s, d_hashes, d_take, n, set_of(h, h->live),
                      set_of(h, h->live ^ 1));
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) h->live ^= 1, h->last = s;
@@ -364,18 +298,11 @@ uint64_t pz_block_walk_scratch_bytes(uint64_t nblocks, uint64_t natt) {
 }
 
 int pz_dev_block_walk(pz_recent_hashes* h, const pz_block_walk_batch* b, void* stream) {
-  int rc = check_walk(h, b, true);
-  if (rc) return rc < 0 ? rc : PZ_OK;
-  if (!aligned16(b->block_hash) || !aligned16(b->log))
-    return fail(PZ_EINVAL, "block walk: block_hash and log must be 16-B aligned device pointers");
-  if ((rc = h->use())) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  hipError_t e = launch_walk(h, *b, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? PZ_OK : hip_fail(e, "pz_block_walk kernels");
+  return enqueue_block_run(check_block_run(h, b, true, "block walk"), h, b, stream, "pz_block_walk kernels", launch_walk);
 }
 
 int pz_block_walk(pz_recent_hashes* h, const pz_block_walk_batch* hb) {
-  int rc = check_walk(h, hb, false);
+  int rc = check_block_run(h, hb, false, "block walk");
   if (rc < 0) return rc;
   if (rc) {  // an empty run: the record says so, the ring stays as it is
     if (hb->result)
@@ -383,53 +310,23 @@ int pz_block_walk(pz_recent_hashes* h, const pz_block_walk_batch* hb) {
       hb->result[kBwCandidateSlot] = hb->has_candidate ? hb->candidate_slot : 0;
     return PZ_OK;
   }
-  const uint64_t nb = hb->nblocks, n = hb->natt;
+  const uint64_t n = hb->natt, log_bytes = pz_block_walk_scratch_bytes(hb->nblocks, n);
   HostForm f(h, "block walk");
   if (f.rc) return f.rc;
   Stager& st = f.st;
-  pz_block_walk_batch d = *hb;
-  d.slot_number = st.up(hb->slot_number, nb);
-  d.report = st.up(hb->report, nb);
-  d.block_hash = st.up(hb->block_hash, nb * 32);
-  if (n) {
-    d.att_block = st.up(hb->att_block, n);
-    d.vote_status = st.up(hb->vote_status, n);
-    d.parents_start = st.up(hb->parents_start, n);
-    if (hb->pend_take) d.pend_take = st.up(hb->pend_take, n);
-  }
-  d.walk = st.up<uint8_t>(nullptr, nb);
-  d.base = st.up<uint64_t>(nullptr, nb);
-  d.result = st.up<uint64_t>(nullptr, kBwResultWords);
-  d.log = st.up<uint8_t>(nullptr, (kBwRing + nb) * 32);
-  if (hb->flags) d.flags = st.up(hb->flags, 1);
+  pz_block_walk_batch d;
+  stage_block_run(st, hb, d, kBwResultWords, log_bytes);
   if (st.rc) return st.rc;
-  st.check(launch_walk(h, d, st.s), "pz_block_walk kernels");
-  st.down(hb->walk, d.walk, nb);
-  st.down(hb->base, d.base, nb);
-  st.down(hb->result, d.result, kBwResultWords);
-  if (hb->log) st.down(hb->log, d.log, (kBwRing + nb) * 32);
-  if (n) {
-    st.down(hb->vote_status, d.vote_status, n);
-    st.down(hb->parents_start, d.parents_start, n);
-    if (hb->pend_take) st.down(hb->pend_take, d.pend_take, n);
-  }
+  st.check(launch_walk(h, d, st.s, nullptr), "pz_block_walk kernels");
+  unstage_block_run(st, hb, d, kBwResultWords, log_bytes);
+  st.down(hb->vote_status, d.vote_status, n);  // (both narrowed in place)
+  if (hb->pend_take) st.down(hb->pend_take, d.pend_take, n);
   return st.sync();
 }
 
 #ifdef PZ_AB_BUILD
-// (tools/blockwalk_probe.py) pz_dev_block_walk with one event pair on each of its three launches;
-// synchronises and returns the milliseconds of scan, rows and roll in ms[0..3).
 int pz_debug_block_walk_timed(pz_recent_hashes* h, const pz_block_walk_batch* b, void* stream, float ms[3]) {
-  int rc = check_walk(h, b, true);
-  if (rc) return rc < 0 ? rc : PZ_OK;
-  if (!ms || !aligned16(b->block_hash) || !aligned16(b->log)) return fail(PZ_EINVAL, "null ms or misaligned pointers");
-  if ((rc = h->use())) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  Events ev;
-  if ((rc = ev.create(4))) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  hipError_t e = launch_walk(h, *b, s, &ev);
-  return ev.elapsed(e == hipSuccess ? PZ_OK : hip_fail(e, "pz_block_walk kernels"), ms, nullptr, 3, s, "timed block walk");
+  return timed_block_run(check_block_run(h, b, true, "block walk"), h, b, stream, ms, "pz_block_walk kernels", launch_walk);
 }
 #endif
 

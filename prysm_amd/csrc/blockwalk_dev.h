@@ -3,8 +3,10 @@
 // updateHead, blockchain/service.go:320-333; IsCycleTransition, core.go:181-183) and the window of
 // ActiveState.RecentBlockHashes each block of the run reads (getSignedParentHashes, core.go:348-360,
 // after computeNewActiveState, core.go:223-237, has appended the earlier candidates' hashes in
-// place on the chain's own ActiveState, service.go:346, :356).  The kernels and the stand-alone CPU
-// check (tests/blockwalk_san.cpp, plain g++ under ASan+UBSan) compile the same text.  No HIP types.
+// place on the chain's own ActiveState, service.go:346, :356) -- block by block first, then a tile
+// of the scan at a time (the carry, the two rounds, the stop), which blockcycle_dev.h's scan takes
+// too.  The kernels and the stand-alone CPU checks (tests/blockwalk_san.cpp and
+// tests/blockcycle_san.cpp, plain g++ under ASan+UBSan) compile the same text.  No HIP types.
 //
 // Which blocks go on is the block gate's report (blockgate_dev.h): go_j = report[j] != 0.  The gate
 // knows nothing of the parent check (service.go:261-269) or of CanProcessBlock (:272, :308): the
@@ -77,6 +79,89 @@ PZ_HD uint8_t bw_walk(bool go, bool cand, bool deferred) {
   return deferred ? kBwDeferred : cand ? kBwCandidate : go ? kBwSaved : kBwOff;
 }
 PZ_HD uint64_t bw_base(uint64_t lag, uint64_t rank, bool deferred) { return deferred ? 0 : 1 - lag + rank; }
+
+// ---- the same rules a tile at a time: what both scan kernels (blockwalk.hip, blockcycle.hip) and
+// the sequential forms of tests/blockwalk_san.cpp and tests/blockcycle_san.cpp compile.  A tile is
+// 1,024 consecutive blocks, a lane each, in 16 waves of 64; lane t of the tile at t0 is block t0 + t.
+constexpr uint32_t kBwTile = 1024, kBwWaves = kBwTile / 64;
+
+// The carry between tiles, the same in every lane: whether a candidate is pending, the largest scan
+// value so far (candidateBlock's slot) and the candidates so far.
+struct BwCarry {
+  bool pending;
+  uint64_t max, cnt;
+};
+PZ_HD BwCarry bw_carry(uint64_t has_candidate, uint64_t candidate_slot) {
+  return BwCarry{has_candidate != 0, has_candidate ? candidate_slot : 0, 0};
+}
+
+// Round 1, once every wave has left its words: s_max[k] wave k's largest bw_scan_value(go, true,
+// slot), s_fgo[k] its first lane that goes on (64: none) and s_fslot[k] that lane's slot.  `before`
+// comes in as the lane's exclusive max over its own wave.  Gives the lane's max_j (before), pending
+// and cand_j, and for the tile the carry's next max and the block that became the candidate with
+// nothing pending (first; kBwNone: none, or something was carried in).
+struct BwRound1 {
+  uint64_t before, tile_max, first;
+  bool pending, cand;
+};
+PZ_HD BwRound1 bw_round1(const BwCarry& c, const uint64_t* s_max, const uint32_t* s_fgo, const uint64_t* s_fslot, uint64_t before,
+                         uint64_t t0, uint32_t w, uint64_t j, bool go, uint64_t slot) {
+  BwRound1 r{before, c.max, kBwNone, false, false};
+  uint64_t fslot = 0;
+  if (c.max > r.before) r.before = c.max;
+  for (uint32_t k = 0; k < kBwWaves; ++k) {
+    const uint64_t m = s_max[k];
+    if (k < w && m > r.before) r.before = m;
+    if (m > r.tile_max) r.tile_max = m;
+    if (!c.pending && r.first == kBwNone && s_fgo[k] < 64) r.first = t0 + 64 * k + s_fgo[k], fslot = s_fslot[k];
+  }
+  // with nothing carried in, the first block that goes on is the candidate whatever its slot
+  r.pending = c.pending || r.first < j;  // (kBwNone < j never holds)
+  if (r.first < j && fslot > r.before) r.before = fslot;
+  if (r.first != kBwNone && bw_scan_value(true, false, fslot) > r.tile_max) r.tile_max = fslot;
+  r.cand = bw_candidate(go, r.pending, slot, r.before);
+  return r;
+}
+
+// Round 2, from the candidates' ballot words (bit l of cand[k]: lane 64 k + l is a candidate): the
+// candidates before lane t of the tile, the carry's included, and the tile's count.
+struct BwRank {
+  uint64_t rank, tile_cnt;
+};
+PZ_HD BwRank bw_rank(const BwCarry& c, const uint64_t* cand, uint32_t t) {
+  BwRank r{c.cnt + (uint64_t)__builtin_popcountll(cand[t >> 6] & ((1ull << (t & 63)) - 1)), 0};
+  for (uint32_t k = 0; k < kBwWaves; ++k) {
+    const uint64_t n = (uint64_t)__builtin_popcountll(cand[k]);
+    if (k < t >> 6) r.rank += n;
+    r.tile_cnt += n;
+  }
+  return r;
+}
+
+// The first set bit at or after tile lane `from` of a tile's ballot words (kBwTile: none).
+PZ_HD uint32_t bw_first(const uint64_t* ballot, uint32_t from) {
+  for (uint32_t k = from >> 6; k < kBwWaves; ++k) {
+    uint64_t m = ballot[k];
+    if (k == from >> 6) m &= ~uint64_t(0) << (from & 63);
+    if (m) return 64 * k + (uint32_t)__builtin_ctzll(m);
+  }
+  return kBwTile;
+}
+
+// The walk's stop in this tile (kBwNone: none), the smallest bw_stop_at of its blocks: its first
+// transition candidate (tr: the candidates with bw_transition(slot, last_state_recalc)), or with lag
+// one past the run's first candidate.  tests/blockwalk_san.cpp holds it against bw_stop_at block by
+// block.
+PZ_HD uint64_t bw_tile_stop(const BwCarry& c, uint64_t t0, uint64_t lag, uint64_t n, const uint64_t* cand, const uint64_t* tr) {
+  const uint32_t ftr = bw_first(tr, 0), fcand = bw_first(cand, 0);
+  uint64_t stop = ftr == kBwTile ? kBwNone : t0 + ftr;
+  if (lag && c.cnt == 0 && fcand != kBwTile && t0 + fcand + 1 < stop) stop = t0 + fcand + 1;
+  return stop >= n ? kBwNone : stop;
+}
+
+PZ_HD void bw_advance(BwCarry& c, const BwRound1& r, uint64_t tile_cnt) {
+  c.cnt += tile_cnt, c.max = r.tile_max, c.pending = c.pending || r.first != kBwNone;
+}
 
 // An attestation row of a block with walk code w and base `base`.
 struct BwRow {

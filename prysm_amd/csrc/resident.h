@@ -77,6 +77,89 @@ const uint8_t* recent_hashes_live(pz_recent_hashes* h);
 hipError_t recent_hashes_roll(pz_recent_hashes* h, const uint8_t* log, const uint64_t* result, const uint32_t* flags, uint64_t nblocks,
                               hipStream_t s);
 
+// The two entry families over a run of blocks against the ring, pz_block_walk (blockwalk.hip) and
+// pz_block_cycle (blockcycle.hip): what their batch structs B share by name -- nblocks, slot_number,
+// report, block_hash, lag, natt, att_block, vote_status, pend_take, parents_start, walk, base,
+// result, log, flags -- checked and staged once.  `what` is "block walk" or "block cycle"; a family
+// adds only its own members, its result's width and its empty run's record.
+
+// Before any launch.  1: an empty run, nothing to launch.
+template <class B>
+int check_block_run(const pz_recent_hashes* h, const B* b, bool device_form, const char* what) {
+  if (!h || !b) return fail(PZ_EINVAL, "%s: null handle or batch", what);
+  if (b->nblocks >= (1ull << 31)) return fail(PZ_EINVAL, "nblocks %llu: 2^31 blocks or more", (unsigned long long)b->nblocks);
+  if (b->lag > 1) return fail(PZ_EINVAL, "lag %llu: 0 or 1", (unsigned long long)b->lag);
+  if (b->nblocks == 0) return 1;
+  if (!b->slot_number || !b->report || !b->block_hash || !b->walk || !b->base || !b->result)
+    return fail(PZ_EINVAL, "%s: null slot_number / report / block_hash / walk / base / result", what);
+  if (device_form && !b->log) return fail(PZ_EINVAL, "%s: null log", what);
+  if (device_form && (!aligned16(b->block_hash) || !aligned16(b->log)))
+    return fail(PZ_EINVAL, "%s: block_hash and log must be 16-B aligned device pointers", what);
+  if (b->natt && (!b->att_block || !b->vote_status || !b->parents_start))
+    return fail(PZ_EINVAL, "%s: null att_block / vote_status / parents_start", what);
+  return PZ_OK;
+}
+
+// The device form behind its check's rc: the family's launches (launch(h, batch, stream, events))
+// on the caller's stream, under the handle's lock.
+template <class B, class Launch>
+int enqueue_block_run(int rc, pz_recent_hashes* h, const B* b, void* stream, const char* what, Launch launch) {
+  if (rc) return rc < 0 ? rc : PZ_OK;
+  Resident* r = resident_of(h);
+  if ((rc = r->use())) return rc;
+  std::lock_guard<std::mutex> lk(r->mu);
+  const hipError_t e = launch(h, *b, static_cast<hipStream_t>(stream), nullptr);
+  return e == hipSuccess ? PZ_OK : hip_fail(e, what);
+}
+
+#ifdef PZ_AB_BUILD
+// (tools/blockwalk_probe.py, tools/blockcycle_probe.py) The same with one event pair on each of the
+// three launches; synchronises and returns the milliseconds of scan, rows and roll in ms[0..3).
+template <class B, class Launch>
+int timed_block_run(int rc, pz_recent_hashes* h, const B* b, void* stream, float ms[3], const char* what, Launch launch) {
+  if (rc) return rc < 0 ? rc : PZ_OK;
+  if (!ms) return fail(PZ_EINVAL, "%s: null ms", what);
+  Resident* r = resident_of(h);
+  if ((rc = r->use())) return rc;
+  std::lock_guard<std::mutex> lk(r->mu);
+  Events ev;
+  if ((rc = ev.create(4))) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const hipError_t e = launch(h, *b, s, &ev);
+  return ev.elapsed(e == hipSuccess ? PZ_OK : hip_fail(e, what), ms, nullptr, 3, s, what);
+}
+#endif
+
+// The host form's staging: d = *hb with the shared members on the device (result_words words of
+// result, log_bytes of log), and after the launches the shared outputs back (log where hb has one).
+template <class B>
+void stage_block_run(Stager& st, const B* hb, B& d, uint64_t result_words, uint64_t log_bytes) {
+  const uint64_t nb = hb->nblocks, n = hb->natt;
+  d = *hb;
+  d.slot_number = st.up(hb->slot_number, nb);
+  d.report = st.up(hb->report, nb);
+  d.block_hash = st.up(hb->block_hash, nb * 32);
+  if (n) {
+    d.att_block = st.up(hb->att_block, n);
+    d.vote_status = st.up(hb->vote_status, n);
+    d.parents_start = st.up(hb->parents_start, n);
+    if (hb->pend_take) d.pend_take = st.up(hb->pend_take, n);
+  }
+  d.walk = st.up<uint8_t>(nullptr, nb);
+  d.base = st.up<uint64_t>(nullptr, nb);
+  d.result = st.up<uint64_t>(nullptr, result_words);
+  d.log = st.up<uint8_t>(nullptr, log_bytes);
+  if (hb->flags) d.flags = st.up(hb->flags, 1);
+}
+template <class B>
+void unstage_block_run(Stager& st, const B* hb, const B& d, uint64_t result_words, uint64_t log_bytes) {
+  st.down(hb->walk, d.walk, hb->nblocks);
+  st.down(hb->base, d.base, hb->nblocks);
+  st.down(hb->result, d.result, result_words);
+  if (hb->log) st.down(hb->log, d.log, log_bytes);
+  st.down(hb->parents_start, d.parents_start, hb->natt);
+}
+
 // The vote cache's lookup side: device pointers, valid for the handle's lifetime.
 struct VcView {
   int device;

@@ -1,36 +1,20 @@
 // The rules of a run across a cycle transition on the CPU under ASan+UBSan: blockcycle_dev.h (the
 // inlines the kernels of blockcycle.hip compile too) driven through a sequential form of the scan
 // kernel -- tiles of 1,024 lanes in waves of 64, the carry and the run's state between tiles, the
-// two rounds a tile with their ballot words -- and of the rows and roll kernels, against a plain
+// two rounds a tile with their ballot words, every lane through the same bw_round1 / bw_rank /
+// bc_tile / bw_advance the kernel calls -- and of the rows and roll kernels, against a plain
 // restatement of blockchain/service.go:320-363 that walks block by block with a pending-candidate
 // variable, a "the candidate's states are not promoted yet" flag, a last_state_recalc that advances
 // at the transition block and a list that only grows (computeNewActiveState, core.go:223-237).
-// Every array has exactly its size.  Prints counts; exit status 0 iff all agree.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
-#include <vector>
-
+// On a run without a transition block the form must also give what the walk's form
+// (walk_sequential, blockscan_san.h) gives.  Every array has exactly its size.  Prints counts; exit
+// status 0 iff all agree.
 #include "../blockcycle_dev.h"
+#include "blockscan_san.h"
 
-using namespace pz;
+using namespace san;
 
 namespace {
-
-constexpr uint64_t kTile = kBcTile, kWave = 64, kWaves = kBcWaves;
-
-struct Run {
-  uint64_t n = 0, has0 = 0, cslot0 = 0, lsr = 0, lag = 0;
-  uint32_t flags = 0;  // the gate's flag word
-  std::vector<uint64_t> slot;
-  std::vector<uint8_t> report, hash;  // n, n x 32
-  std::vector<uint8_t> ring, ring_len;  // 129 x 32, 129
-  std::vector<uint32_t> att_block;
-  std::vector<uint64_t> parents_start;
-  std::vector<uint8_t> pend_take;
-  std::vector<int32_t> vote_status;
-};
 
 struct Out {
   std::vector<uint8_t> walk, log, ring, ring_len, take0, take1;
@@ -124,8 +108,7 @@ Out sequential(const Run& r) {
   }
   // scan
   std::memcpy(o.log.data(), r.ring.data(), kBwRing * 32);
-  bool c_pending = r.has0 != 0;
-  uint64_t c_max = c_pending ? r.cslot0 : 0, c_cnt = 0;
+  BwCarry c = bw_carry(r.has0, r.cslot0);
   uint64_t fin_rank = 0, fin_pending = 0, fin_before = 0, fin_slot = 0, fin_trank = 0, fin_tslot = 0;
   BcState st = bc_start(lag), by_rule = bc_start(lag);
   for (uint64_t t0 = 0; t0 < n; t0 += kTile) {
@@ -133,63 +116,25 @@ Out sequential(const Run& r) {
       for (uint64_t j = t0; j < n && j < t0 + kTile; ++j) o.walk[j] = kBwDeferred, o.base[j] = 0;
       continue;
     }
-    bool go[kTile];
-    uint64_t slot[kTile], before[kTile], s_max[kWaves], s_fslot[kWaves], s_cb[kWaves], s_tb[kWaves], s_ta[kWaves];
-    uint32_t s_fgo[kWaves];
-    for (uint64_t w = 0; w < kWaves; ++w) {  // round 1
-      uint64_t inc = 0;
-      s_fgo[w] = 64, s_fslot[w] = 0;
-      for (uint64_t l = 0; l < kWave; ++l) {
-        const uint64_t t = w * kWave + l, j = t0 + t;
-        go[t] = j < n && bw_go(r.report[j]);
-        slot[t] = j < n ? r.slot[j] : 0;
-        before[t] = inc;
-        const uint64_t v = bw_scan_value(go[t], true, slot[t]);
-        if (v > inc) inc = v;
-        if (go[t] && s_fgo[w] == 64) s_fgo[w] = (uint32_t)l, s_fslot[w] = slot[t];
-      }
-      s_max[w] = inc;
-    }
-    uint64_t tile_max = c_max, first = kBwNone, fslot = 0;
-    for (uint64_t k = 0; k < kWaves; ++k) {
-      if (s_max[k] > tile_max) tile_max = s_max[k];
-      if (!c_pending && first == kBwNone && s_fgo[k] < 64) first = t0 + 64 * k + s_fgo[k], fslot = s_fslot[k];
-    }
-    if (first != kBwNone && bw_scan_value(true, false, fslot) > tile_max) tile_max = fslot;
-    bool cand[kTile], pending[kTile];
-    for (uint64_t t = 0; t < kTile; ++t) {
-      const uint64_t w = t / kWave, j = t0 + t;
-      if (c_max > before[t]) before[t] = c_max;
-      for (uint64_t k = 0; k < w; ++k)
-        if (s_max[k] > before[t]) before[t] = s_max[k];
-      pending[t] = c_pending || first < j;
-      if (first < j && fslot > before[t]) before[t] = fslot;
-      cand[t] = bw_candidate(go[t], pending[t], slot[t], before[t]);
-    }
+    Tile t;
+    uint64_t tb[kWaves], ta[kWaves];
+    round1(r, c, t0, t);
+    ballot(t, tb, [&r](uint64_t slot) { return bw_transition(slot, r.lsr); });  // round 2: the ballot words
+    ballot(t, ta, [lsr_after](uint64_t slot) { return bw_transition(slot, lsr_after); });
+    bc_tile(st, t0, lag, t.cb, tb, ta);
     uint64_t tile_cnt = 0;
-    for (uint64_t w = 0; w < kWaves; ++w) {  // round 2: the ballot words
-      s_cb[w] = s_tb[w] = s_ta[w] = 0;
-      for (uint64_t l = 0; l < kWave; ++l) {
-        const uint64_t t = w * kWave + l;
-        if (!cand[t]) continue;
-        s_cb[w] |= 1ull << l, ++tile_cnt;
-        if (bw_transition(slot[t], r.lsr)) s_tb[w] |= 1ull << l;
-        if (bw_transition(slot[t], lsr_after)) s_ta[w] |= 1ull << l;
-      }
-    }
-    bc_tile(st, t0, lag, s_cb, s_tb, s_ta);
-    uint64_t rank = c_cnt;
-    for (uint64_t t = 0; t < kTile; ++t) {
-      const uint64_t j = t0 + t;
-      if (j >= n) break;
-      if (cand[t]) bc_candidate(by_rule, j, slot[t], r.lsr, lag);  // (the per-block statement, which the tile's must equal)
+    for (uint64_t i = 0; i < kTile && t0 + i < n; ++i) {
+      const uint64_t j = t0 + i;
+      const BwRound1& x = t.r1[i];
+      const BwRank k = rank_of(c, t, i);
+      if (x.cand) bc_candidate(by_rule, j, t.slot[i], r.lsr, lag);  // (the per-block statement, which the tile's must equal)
       const bool deferred = bc_deferred(st, j);
-      o.walk[j] = bw_walk(go[t], cand[t], deferred);
-      o.base[j] = bc_base(bc_lagged(st, lag, j), rank, deferred);
-      if (cand[t] && !deferred) std::memcpy(&o.log[32 * (kBwRing + rank)], &r.hash[32 * j], 32);
-      if (j == st.t_index) fin_trank = rank, fin_tslot = slot[t];
-      if (j == st.l_index) fin_rank = rank, fin_pending = pending[t], fin_before = before[t], fin_slot = slot[t];
-      rank += cand[t];
+      o.walk[j] = bw_walk(t.go[i], x.cand, deferred);
+      o.base[j] = bc_base(bc_lagged(st, lag, j), k.rank, deferred);
+      if (x.cand && !deferred) std::memcpy(&o.log[32 * (kBwRing + k.rank)], &r.hash[32 * j], 32);
+      if (j == st.t_index) fin_trank = k.rank, fin_tslot = t.slot[i];
+      if (j == st.l_index) fin_rank = k.rank, fin_pending = x.pending, fin_before = x.before, fin_slot = t.slot[i];
+      tile_cnt = k.tile_cnt;
     }
     if (by_rule.t_index != st.t_index || by_rule.l_index != st.l_index || by_rule.stop != st.stop || by_rule.lag_out != st.lag_out) {
       std::printf("FAIL: tile state (%llu %llu %llu %llu), by rule (%llu %llu %llu %llu)\n", (unsigned long long)st.t_index,
@@ -198,14 +143,14 @@ Out sequential(const Run& r) {
                   (unsigned long long)by_rule.lag_out);
       std::exit(1);
     }
-    c_cnt += tile_cnt, c_max = tile_max, c_pending = c_pending || first != kBwNone;
+    bw_advance(c, t.r1[0], tile_cnt);
   }
   const bool met = st.l_index != kBwNone, included = met && st.stop == st.l_index + 1;
-  const uint64_t ncand = met ? fin_rank + (included ? 1 : 0) : c_cnt;
+  const uint64_t ncand = met ? fin_rank + (included ? 1 : 0) : c.cnt;
   o.result[kBwStop] = st.stop == kBwNone ? n : st.stop;
   o.result[kBwNcand] = ncand;
-  o.result[kBwHasCandidate] = included ? 1 : met ? fin_pending : (uint64_t)c_pending;
-  o.result[kBwCandidateSlot] = included ? fin_slot : met ? fin_before : c_max;
+  o.result[kBwHasCandidate] = included ? 1 : met ? fin_pending : (uint64_t)c.pending;
+  o.result[kBwCandidateSlot] = included ? fin_slot : met ? fin_before : c.max;
   o.result[kBcTIndex] = st.t_index, o.result[kBcTRank] = fin_trank, o.result[kBcTSlot] = fin_tslot, o.result[kBcLagOut] = st.lag_out;
   for (uint64_t p = 32 * (kBwRing + ncand); p < 32 * (kBwRing + n); ++p) o.log[p] = 0;
   // rows
@@ -216,27 +161,43 @@ Out sequential(const Run& r) {
                            o.result[kBcTIndex]);
     o.parents_start[i] = x.parents_start, o.vote0[i] = x.vote0, o.vote1[i] = x.vote1, o.take0[i] = x.take0, o.take1[i] = x.take1;
   }
-  // roll
-  std::vector<uint8_t> to(kBwRing * 32), to_len(kBwRing);
-  const uint64_t nroll = bw_roll_count(ncand, r.flags);
-  for (uint64_t k = 0; k < kBwRing; ++k) {
-    const uint64_t src = bw_roll_src(k, nroll);
-    std::memcpy(&to[32 * k], &o.log[32 * src], 32);
-    to_len[k] = bw_roll_len(r.ring_len[k], nroll);
-  }
-  o.ring = to, o.ring_len = to_len;
+  roll(r, o.log, ncand, o.ring, o.ring_len);
   return o;
 }
 
-uint64_t g_runs, g_blocks, g_deferred, g_saved, g_cands, g_rows, g_with_t, g_l_deferred, g_lag_t, g_after;
+uint64_t g_runs, g_blocks, g_deferred, g_saved, g_cands, g_rows, g_with_t, g_l_deferred, g_lag_t, g_after, g_walks, g_walks_lag, g_walks_early;
 
-template <class T>
-void same(const std::vector<T>& a, const std::vector<T>& b, const char* what, const char* name) {
-  if (a == b) return;
-  size_t i = 0;
-  while (i < a.size() && i < b.size() && a[i] == b[i]) ++i;
-  std::printf("FAIL %s: %s differs at %zu (sizes %zu, %zu)\n", name, what, i, a.size(), b.size());
-  std::exit(1);
+// A run in which no candidate at or before the walk's stop is a transition: the walk's form stops at
+// the run's end, or with lag behind its one candidate (a transition candidate stops the walk before
+// itself, with none taken under lag).  There the cycle's form must be the walk's: the same record,
+// codes, bases, log and ring, phase 0 the walk's narrowed columns, phase 1 empty and no T.
+void agree_with_walk(const Run& r, const Out& g, const char* name) {
+  const WalkOut w = walk_sequential(r);
+  if (!(w.result[kBwStop] == r.n || (r.lag && w.result[kBwNcand] == 1))) return;
+  for (int k = 0; k < kBwResultWords; ++k)
+    if (w.result[k] != g.result[k]) {
+      std::printf("FAIL %s: result[%d] %llu, the walk's %llu\n", name, k, (unsigned long long)g.result[k], (unsigned long long)w.result[k]);
+      std::exit(1);
+    }
+  if (r.n && g.result[kBcTIndex] != kBwNone) {
+    std::printf("FAIL %s: t_index %llu on a run the walk takes whole\n", name, (unsigned long long)g.result[kBcTIndex]);
+    std::exit(1);
+  }
+  std::vector<int32_t> narrowed = r.vote_status;
+  for (auto& v : narrowed) v = bc_narrow(v);
+  same(w.walk, g.walk, "walk (the walk's)", name);
+  same(w.base, g.base, "base (the walk's)", name);
+  same(w.log, g.log, "log (the walk's)", name);
+  same(w.ring, g.ring, "ring (the walk's)", name);
+  same(w.ring_len, g.ring_len, "ring lengths (the walk's)", name);
+  same(w.parents_start, g.parents_start, "parents_start (the walk's)", name);
+  if (r.n) {  // (an empty run launches nothing: the rows' columns stay as they were)
+    same(w.vote_status, g.vote0, "vote0 (the walk's vote_status)", name);
+    same(w.pend_take, g.take0, "take0 (the walk's pend_take)", name);
+    same(narrowed, g.vote1, "vote1 (all narrowed)", name);
+    same(std::vector<uint8_t>(r.att_block.size(), 0), g.take1, "take1 (all zero)", name);
+  }
+  ++g_walks, g_walks_lag += r.lag, g_walks_early += w.result[kBwStop] < r.n;
 }
 
 void check(const Run& r, const char* name) {
@@ -272,33 +233,7 @@ void check(const Run& r, const char* name) {
   g_with_t += t, g_lag_t += t && r.lag;
   g_l_deferred += t && !r.lag && e.result[kBcLagOut] && e.result[kBwStop] < r.n;
   for (size_t i = 0; i < e.vote1.size(); ++i) g_after += e.vote1[i] == PZ_ATT_PROCESSED || e.take1[i];
-}
-
-std::mt19937_64 rng(20182);
-
-// go: 0 none, 1 all, 2 alternating, 3 random.  slot_of gives block j's slot.
-template <class F>
-Run make(uint64_t n, int go, F slot_of, uint64_t has0, uint64_t cslot0, uint64_t lsr, uint64_t lag) {
-  Run r;
-  r.n = n, r.has0 = has0, r.cslot0 = cslot0, r.lsr = lsr, r.lag = lag;
-  r.flags = rng() % 8 == 0;
-  r.slot.resize(n), r.report.resize(n), r.hash.resize(32 * n);
-  for (uint64_t j = 0; j < n; ++j) {
-    r.slot[j] = slot_of(j);
-    r.report[j] = go == 0 ? 0 : go == 1 ? 1 + j % 2 : go == 2 ? j % 2 : (rng() % 4 ? 1 + rng() % 2 : 0);
-  }
-  for (auto& b : r.hash) b = (uint8_t)rng();
-  r.ring.resize(kBwRing * 32), r.ring_len.resize(kBwRing);
-  for (auto& b : r.ring) b = (uint8_t)rng();
-  for (auto& l : r.ring_len) l = rng() % 3 ? 32 : (uint8_t)(rng() % 33);
-  for (uint64_t j = 0; j < n; ++j)
-    for (uint64_t k = rng() % 4; k > 0; --k) {
-      r.att_block.push_back((uint32_t)j);
-      r.parents_start.push_back(rng() % 65);
-      r.pend_take.push_back(rng() % 2);
-      r.vote_status.push_back((int32_t)(rng() % 3 ? PZ_ATT_PROCESSED : rng() % 8));
-    }
-  return r;
+  agree_with_walk(r, g, name);
 }
 
 void fixed_cases() {
@@ -371,15 +306,31 @@ void random_runs(int count) {
   }
 }
 
+// Runs the walk takes too, at both sides of a wave's and a tile's edge: a last_state_recalc no slot reaches.
+void walk_runs() {
+  const uint64_t far = 1ull << 40;
+  for (uint64_t n : {uint64_t(1), uint64_t(64), uint64_t(65), uint64_t(1023), uint64_t(1024), uint64_t(1025), uint64_t(2049)})
+    for (uint64_t lag = 0; lag < 2; ++lag)
+      for (int k = 0; k < 8; ++k) {
+        const uint64_t at = rng() % (n + 1), step = 1 + rng() % 3;  // under lag: the first candidate, anywhere
+        check(make(n, k % 2 ? 3 : 1, [at, step](uint64_t j) { return j < at ? 5 : 6 + j / step; }, 1, 5, far, lag), "the walk's run");
+        check(make(n, 3, [](uint64_t) { return rng() % 90; }, rng() % 2, rng() % 90, far, lag), "the walk's run, slots anywhere");
+      }
+}
+
 }  // namespace
 
 int main() {
+  rng.seed(20182);
   fixed_cases();
   random_runs(4000);
+  walk_runs();
   std::printf("ok: %llu runs, %llu blocks, %llu deferred, %llu saved-not-candidate, %llu candidates, %llu rows, %llu with T, "
               "%llu with L deferred, %llu with T under lag, %llu rows after T\n",
               (unsigned long long)g_runs, (unsigned long long)g_blocks, (unsigned long long)g_deferred, (unsigned long long)g_saved,
               (unsigned long long)g_cands, (unsigned long long)g_rows, (unsigned long long)g_with_t, (unsigned long long)g_l_deferred,
               (unsigned long long)g_lag_t, (unsigned long long)g_after);
+  std::printf("the walk's runs: %llu, %llu under lag, %llu stopped early\n", (unsigned long long)g_walks, (unsigned long long)g_walks_lag,
+              (unsigned long long)g_walks_early);
   return 0;
 }

@@ -1,41 +1,17 @@
 // The block walk's rules on the CPU under ASan+UBSan: blockwalk_dev.h (the inlines the kernels of
 // blockwalk.hip compile too) driven through a sequential form of the scan kernel -- tiles of 1,024
-// lanes in waves of 64, the carry between tiles, the two rounds a tile -- and of the rows, roll and
-// append kernels, against a plain restatement of blockchain/service.go:320-333 that walks block by
+// lanes in waves of 64, the carry between tiles, the two rounds a tile, every lane through the same
+// bw_round1 / bw_rank / bw_tile_stop / bw_advance the kernel calls (walk_sequential,
+// blockscan_san.h) -- and of the rows, roll and append kernels, against a plain restatement of blockchain/service.go:320-333 that walks block by
 // block with a pending-candidate variable and a list that only grows (computeNewActiveState,
 // core.go:223-237).  Every array has exactly its size.  Prints counts; exit status 0 iff all agree.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
-#include <vector>
+#include "blockscan_san.h"
 
-#include "../blockwalk_dev.h"
-
-using namespace pz;
+using namespace san;
 
 namespace {
 
-constexpr uint64_t kTile = 1024, kWave = 64, kWaves = kTile / kWave;
-
-struct Run {
-  uint64_t n = 0, has0 = 0, cslot0 = 0, lsr = 0, lag = 0;
-  uint32_t flags = 0;  // the gate's flag word
-  std::vector<uint64_t> slot;
-  std::vector<uint8_t> report, hash;  // n, n x 32
-  std::vector<uint8_t> ring, ring_len;  // 129 x 32, 129
-  std::vector<uint32_t> att_block;
-  std::vector<uint64_t> parents_start;
-  std::vector<uint8_t> pend_take;
-  std::vector<int32_t> vote_status;
-};
-
-struct Out {
-  std::vector<uint8_t> walk, log, ring, ring_len, pend_take;
-  std::vector<uint64_t> base, parents_start;
-  std::vector<int32_t> vote_status;
-  uint64_t result[kBwResultWords] = {};
-};
+using Out = WalkOut;
 
 // ---- the reference, block by block ---------------------------------------------------------------
 Out reference(const Run& r) {
@@ -91,140 +67,10 @@ Out reference(const Run& r) {
   return o;
 }
 
-// ---- the kernels, lane by lane ---------------------------------------------------------------------
-Out sequential(const Run& r) {
-  Out o;
-  const uint64_t n = r.n;
-  o.walk.assign(n, 0xEE);
-  o.base.assign(n, 0xEEEE);
-  o.log.assign((kBwRing + n) * 32, 0xEE);
-  o.ring = r.ring, o.ring_len = r.ring_len;
-  o.parents_start = r.parents_start, o.pend_take = r.pend_take, o.vote_status = r.vote_status;
-  if (n == 0) {  // nothing is launched; the host form's record
-    o.result[kBwHasCandidate] = r.has0 != 0, o.result[kBwCandidateSlot] = r.has0 ? r.cslot0 : 0;
-    o.log = r.ring;
-    return o;
-  }
-  // scan
-  std::memcpy(o.log.data(), r.ring.data(), kBwRing * 32);
-  bool c_pending = r.has0 != 0, fin_set = false;
-  uint64_t c_max = c_pending ? r.cslot0 : 0, c_cnt = 0, c_stop = kBwNone, fin[3] = {};
-  for (uint64_t t0 = 0; t0 < n; t0 += kTile) {
-    if (c_stop != kBwNone) {
-      for (uint64_t j = t0; j < n && j < t0 + kTile; ++j) o.walk[j] = kBwDeferred, o.base[j] = 0;
-      continue;
-    }
-    bool go[kTile];
-    uint64_t slot[kTile], before[kTile], s_max[kWaves], s_fslot[kWaves];
-    uint32_t s_fgo[kWaves], s_cnt[kWaves], s_fcand[kWaves], s_ftr[kWaves];
-    for (uint64_t w = 0; w < kWaves; ++w) {  // round 1
-      uint64_t inc = 0;
-      s_fgo[w] = 64, s_fslot[w] = 0;
-      for (uint64_t l = 0; l < kWave; ++l) {
-        const uint64_t t = w * kWave + l, j = t0 + t;
-        go[t] = j < n && bw_go(r.report[j]);
-        slot[t] = j < n ? r.slot[j] : 0;
-        before[t] = inc;
-        const uint64_t v = bw_scan_value(go[t], true, slot[t]);
-        if (v > inc) inc = v;
-        if (go[t] && s_fgo[w] == 64) s_fgo[w] = (uint32_t)l, s_fslot[w] = slot[t];
-      }
-      s_max[w] = inc;
-    }
-    uint64_t tile_max = c_max, first = kBwNone, fslot = 0;
-    for (uint64_t k = 0; k < kWaves; ++k) {
-      if (s_max[k] > tile_max) tile_max = s_max[k];
-      if (!c_pending && first == kBwNone && s_fgo[k] < 64) first = t0 + 64 * k + s_fgo[k], fslot = s_fslot[k];
-    }
-    if (first != kBwNone && bw_scan_value(true, false, fslot) > tile_max) tile_max = fslot;
-    bool cand[kTile], pending[kTile];
-    for (uint64_t t = 0; t < kTile; ++t) {
-      const uint64_t w = t / kWave, j = t0 + t;
-      if (c_max > before[t]) before[t] = c_max;
-      for (uint64_t k = 0; k < w; ++k)
-        if (s_max[k] > before[t]) before[t] = s_max[k];
-      pending[t] = c_pending || first < j;
-      if (first < j && fslot > before[t]) before[t] = fslot;
-      cand[t] = bw_candidate(go[t], pending[t], slot[t], before[t]);
-    }
-    for (uint64_t w = 0; w < kWaves; ++w) {  // round 2
-      s_cnt[w] = 0, s_fcand[w] = 64, s_ftr[w] = 64;
-      for (uint64_t l = 0; l < kWave; ++l) {
-        const uint64_t t = w * kWave + l;
-        if (!cand[t]) continue;
-        ++s_cnt[w];
-        if (s_fcand[w] == 64) s_fcand[w] = (uint32_t)l;
-        if (bw_transition(slot[t], r.lsr) && s_ftr[w] == 64) s_ftr[w] = (uint32_t)l;
-      }
-    }
-    uint64_t tile_cnt = 0, fcand = kBwNone, ftr = kBwNone;
-    for (uint64_t k = 0; k < kWaves; ++k) {
-      tile_cnt += s_cnt[k];
-      if (fcand == kBwNone && s_fcand[k] < 64) fcand = t0 + 64 * k + s_fcand[k];
-      if (ftr == kBwNone && s_ftr[k] < 64) ftr = t0 + 64 * k + s_ftr[k];
-    }
-    uint64_t stop = ftr;
-    if (r.lag && c_cnt == 0 && fcand != kBwNone && fcand + 1 < stop) stop = fcand + 1;
-    if (stop >= n) stop = kBwNone;
-    uint64_t rank = c_cnt, stop_by_rule = kBwNone;
-    for (uint64_t t = 0; t < kTile; ++t) {
-      const uint64_t j = t0 + t;
-      if (j >= n) break;
-      // (the per-block statement of the stop, which the tile's two firsts must equal)
-      const uint64_t s = bw_stop_at(j, cand[t], rank, slot[t], r.lsr, r.lag);
-      if (s < stop_by_rule) stop_by_rule = s;
-      const bool deferred = j >= stop;
-      o.walk[j] = bw_walk(go[t], cand[t], deferred);
-      o.base[j] = bw_base(r.lag, rank, deferred);
-      if (cand[t] && !deferred) std::memcpy(&o.log[32 * (kBwRing + rank)], &r.hash[32 * j], 32);
-      if (j == stop) fin[0] = rank, fin[1] = pending[t], fin[2] = before[t], fin_set = true;
-      rank += cand[t];
-    }
-    if ((stop_by_rule >= n ? kBwNone : stop_by_rule) != stop) {
-      std::printf("FAIL: tile stop %llu, by rule %llu\n", (unsigned long long)stop, (unsigned long long)stop_by_rule);
-      std::exit(1);
-    }
-    c_stop = stop;
-    c_cnt += tile_cnt, c_max = tile_max, c_pending = c_pending || first != kBwNone;
-  }
-  const uint64_t ncand = fin_set ? fin[0] : c_cnt;
-  o.result[kBwStop] = c_stop == kBwNone ? n : c_stop;
-  o.result[kBwNcand] = ncand;
-  o.result[kBwHasCandidate] = fin_set ? fin[1] : (uint64_t)c_pending;
-  o.result[kBwCandidateSlot] = fin_set ? fin[2] : c_max;
-  for (uint64_t p = 32 * (kBwRing + ncand); p < 32 * (kBwRing + n); ++p) o.log[p] = 0;
-  // rows
-  for (size_t i = 0; i < r.att_block.size(); ++i) {
-    const uint64_t b = r.att_block[i];
-    if (b >= n) continue;
-    const BwRow x = bw_row(o.parents_start[i], o.pend_take[i], o.vote_status[i], o.walk[b], o.base[b]);
-    o.parents_start[i] = x.parents_start, o.pend_take[i] = x.pend_take, o.vote_status[i] = x.vote_status;
-  }
-  // roll
-  std::vector<uint8_t> to(kBwRing * 32), to_len(kBwRing);
-  const uint64_t nroll = bw_roll_count(ncand, r.flags);
-  for (uint64_t k = 0; k < kBwRing; ++k) {
-    const uint64_t src = bw_roll_src(k, nroll);
-    std::memcpy(&to[32 * k], &o.log[32 * src], 32);
-    to_len[k] = bw_roll_len(r.ring_len[k], nroll);
-  }
-  o.ring = to, o.ring_len = to_len;
-  return o;
-}
-
 uint64_t g_runs, g_blocks, g_deferred, g_saved, g_cands, g_rows, g_appends;
 
-template <class T>
-void same(const std::vector<T>& a, const std::vector<T>& b, const char* what, const char* name) {
-  if (a == b) return;
-  size_t i = 0;
-  while (i < a.size() && i < b.size() && a[i] == b[i]) ++i;
-  std::printf("FAIL %s: %s differs at %zu (sizes %zu, %zu)\n", name, what, i, a.size(), b.size());
-  std::exit(1);
-}
-
 void check(const Run& r, const char* name) {
-  const Out e = reference(r), g = sequential(r);
+  const Out e = reference(r), g = walk_sequential(r);
   if (r.n) {
     same(e.walk, g.walk, "walk", name);
     same(e.base, g.base, "base", name);
@@ -242,33 +88,6 @@ void check(const Run& r, const char* name) {
   same(e.vote_status, g.vote_status, "vote_status", name);
   ++g_runs, g_blocks += r.n, g_rows += r.att_block.size();
   for (uint8_t w : e.walk) g_deferred += w == kBwDeferred, g_saved += w == kBwSaved, g_cands += w == kBwCandidate;
-}
-
-std::mt19937_64 rng(20181);
-
-// go: 0 none, 1 all, 2 alternating, 3 random.  slot_of gives block j's slot.
-template <class F>
-Run make(uint64_t n, int go, F slot_of, uint64_t has0, uint64_t cslot0, uint64_t lsr, uint64_t lag) {
-  Run r;
-  r.n = n, r.has0 = has0, r.cslot0 = cslot0, r.lsr = lsr, r.lag = lag;
-  r.flags = rng() % 8 == 0;
-  r.slot.resize(n), r.report.resize(n), r.hash.resize(32 * n);
-  for (uint64_t j = 0; j < n; ++j) {
-    r.slot[j] = slot_of(j);
-    r.report[j] = go == 0 ? 0 : go == 1 ? 1 + j % 2 : go == 2 ? j % 2 : (rng() % 4 ? 1 + rng() % 2 : 0);
-  }
-  for (auto& b : r.hash) b = (uint8_t)rng();
-  r.ring.resize(kBwRing * 32), r.ring_len.resize(kBwRing);
-  for (auto& b : r.ring) b = (uint8_t)rng();
-  for (auto& l : r.ring_len) l = rng() % 3 ? 32 : (uint8_t)(rng() % 33);
-  for (uint64_t j = 0; j < n; ++j)
-    for (uint64_t k = rng() % 4; k > 0; --k) {
-      r.att_block.push_back((uint32_t)j);
-      r.parents_start.push_back(rng() % 65);
-      r.pend_take.push_back(rng() % 2);
-      r.vote_status.push_back((int32_t)(rng() % 3 ? PZ_ATT_PROCESSED : rng() % 8));
-    }
-  return r;
 }
 
 void fixed_cases() {
@@ -353,6 +172,7 @@ void appends() {
 }  // namespace
 
 int main() {
+  rng.seed(20181);
   fixed_cases();
   random_runs(3000);
   appends();

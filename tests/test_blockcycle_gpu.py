@@ -4,7 +4,8 @@ blockchain.ResidentChain):
 1. the three launches of pz_[dev_]block_cycle on synthetic columns, device and host forms, against a
    block-by-block Python restatement of blockchain/service.go:320-363 (a pending candidate, a "not
    promoted yet" flag, a last_state_recalc that advances at the transition block, a list that only
-   grows), with canary bytes behind every output and behind the log;
+   grows), with canary bytes behind every output and behind the log; and on runs without a transition
+   block against the launches of pz_dev_block_walk on the same columns;
 2. the 130-block chain through ResidentChain.process_all: three calls, cut at (0, 65), (65, 64) and
    (129, 1), against oracle.replay.Chain stepped block by block;
 3. the same chain cut right after the transition block: lag 1 comes out, the next call takes it;
@@ -29,6 +30,7 @@ from prysm_amd.votes import DeviceVoteCache
 from test_attpool_gpu import as_pb, table
 from test_blockparents_gpu import block_hash, chain130
 from test_blockwalk_gpu import CANARY, CAPS, check_digests, padded, ring_of
+from test_blockwalk_gpu import run_device as walk_device
 from test_votecache_gpu import snapshot, want
 
 pytestmark = pytest.mark.gpu
@@ -240,6 +242,31 @@ def test_launches_on_synthetic_columns(n, form):
         assert {("T", "no lag", "no lag out", "cut"), ("T", "no lag", "lag out", "cut"), ("T", "no lag", "lag out", "whole"),
                 ("no T", "no lag", "no lag out", "whole"), ("T", "lag", "lag out", "cut"), ("no T", "lag", "no lag out", "cut"),
                 ("no T", "lag", "lag out", "whole"), "rows after T"} <= kinds
+
+
+@pytest.mark.parametrize("lag", [0, 1])
+@pytest.mark.parametrize("n", [65, 1025])
+def test_a_run_without_a_transition_block_is_the_walks(n, lag):
+    """Where no candidate reaches last_state_recalc + 64 the cycle's three launches give what the
+    walk's give on the same columns: the walk's record, codes, bases, log and ring, phase 0 the
+    walk's narrowed columns, phase 1 empty and no T -- past a wave's and a tile's edge, whole
+    (lag 0) and stopped behind the first candidate (lag 1)."""
+    rng = np.random.default_rng(3000 + 2 * n + lag)
+    mk = lambda *a, **kw: make(rng, n, *a, lsr=FAR, lag=lag, **kw)  # noqa: E731
+    stops = set()
+    for name, r in [("all", mk("all", lambda j: 2 + j)), ("random", mk("random", lambda j: int(rng.integers(0, 90)), has0=1, cslot0=40)),
+                    ("the first candidate in the last wave", mk("alt", lambda j: 5 if j < n - 2 else 6 + j, has0=1, cslot0=5))]:
+        w, c = walk_device(r), run_device(r)
+        np.testing.assert_array_equal(c["result"][:4], w["result"], name)
+        assert int(c["result"][4]) == NONE, name
+        for k in ("walk", "base", "log", "ring", "ring_len", "parents_start"):
+            np.testing.assert_array_equal(c[k], w[k], "%s: %s" % (name, k))
+        np.testing.assert_array_equal(c["vote0"], w["vote_status"], name)
+        np.testing.assert_array_equal(c["take0"], w["pend_take"], name)
+        np.testing.assert_array_equal(c["vote1"], np.where(r["vote_status"] == PROCESSED, NOT_PROCESSED, r["vote_status"]), name)
+        assert not c["take1"].any(), name
+        stops.add(int(w["result"][0]) < n)
+    assert stops == ({True} if lag else {False})  # (lag 1: every run here has a candidate before its last block)
 
 
 # ---- 2: the 130-block chain in three calls --------------------------------------------------------------------

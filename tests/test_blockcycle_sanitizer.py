@@ -9,7 +9,9 @@ last_state_recalc that advances at the transition block and a list that only gro
 at lanes 1,022, 1,023 and 1,024 with the promoting block in the next tile; siblings and closed blocks
 between the two; the promoting block a transition itself (deferred); the run ending before it; lag 1
 with its first candidate plain and a transition; slots 0 and 1; last_state_recalc near 2^64; and
-4,000 random runs, over arrays of exactly their sizes.  Built by ``make -C prysm_amd/csrc
+4,000 random runs, over arrays of exactly their sizes.  On every run without a transition block
+(among them runs of {1, 64, 65, 1023, 1024, 1025, 2049} blocks with lag 0 and 1 against a
+last_state_recalc no slot reaches) the cycle's form is also held against the walk's.  Built by ``make -C prysm_amd/csrc
 san_blockcycle`` and run directly; no GPU code is involved and nothing is loaded into Python."""
 import os
 import re
@@ -28,4 +30,9 @@ def test_block_cycle_rules_clean_and_consistent_under_sanitizer():
     runs, blocks, deferred, saved, cands, rows, with_t, l_deferred, lag_t, after = (int(x) for x in m.groups())
     assert runs > 1000 and deferred > 1000 and saved > 1000 and cands > 1000 and rows > 100000, r.stdout
     assert with_t > 1000 and l_deferred > 100 and lag_t > 100 and after > 10000, r.stdout  # no class is silently empty
+    # the runs without a transition block, on which the cycle's form must equal the walk's
+    w = re.search(r"^the walk's runs: (\d+), (\d+) under lag, (\d+) stopped early$", r.stdout, re.M)
+    assert w, r.stdout
+    walks, walks_lag, walks_early = (int(x) for x in w.groups())
+    assert walks > 1000 and walks_lag > 100 and walks_early > 100, r.stdout
     assert "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr
