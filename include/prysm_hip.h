@@ -1443,6 +1443,92 @@ int pz_crystallized_state_read(pz_recalc_state* st, const pz_cstate_rest* rest, 
                                uint64_t nval, const uint8_t* d_field12, uint64_t field12_len, uint8_t* out /* host */,
                                uint64_t cap, uint64_t* len, uint8_t root[32] /* optional */);
 
+/* ---- a2 / R: the stored CrystallizedState read back into the resident objects' columns ---------------
+ * NewBeaconChain over a database that holds a state (blockchain/core.go:86-95) for the resident path:
+ * replaces proto.Unmarshal of messages.pb.go's CrystallizedState (one heap object per validator) and
+ * the repacking into columns.  The inverse of pz_crystallized_state_read: the bytes it emits load back
+ * into the same columns.  Exactly the canonical encoding is accepted -- what proto.Marshal emits and
+ * PersistCrystallizedState stores (core.go:170-177): field order, minimal varints, zero scalars and
+ * empty bytes absent, packed members, no unknown field, no trailing byte.  Anything else is PZ_EINVAL
+ * with the offset of the key byte of the first field that breaks the rule (for a run of records that
+ * ends where no header stands: that position); pz_chain_new_from_state's host reader stays the lenient
+ * path for such input.  prysm_amd/csrc/unwire_state_dev.h states the rules; DESIGN.md §3 the launches.
+ *
+ * pz_cstate_head: host only, no device (as pz_count_attestations).  Fields 1-10 of cstate[0, len): the
+ * PZ_RS_* scalars and the crosslink records as pz_recalc_state_new takes them (rec_hash_offs: nrec + 1
+ * entries; rec_hash must hold the hashes' total, below len), *rest the fields the handle does not hold,
+ * *body_beg the offset of the first byte behind field 10.  PZ_ERANGE with *nrec set when rec_cap is too
+ * small (call again); PZ_EINVAL with *body_beg = the violation's offset when the head is not canonical
+ * (a dynasty_seed above 64 bytes included). */
+int pz_cstate_head(const uint8_t* cstate, uint64_t len, uint64_t scalars[PZ_RS_COUNT], pz_cstate_rest* rest,
+                   uint64_t* rec_dynasty, uint64_t* rec_slot, uint8_t* rec_hash, uint64_t* rec_hash_offs, uint64_t rec_cap,
+                   uint64_t* nrec, uint64_t* body_beg);
+/* pz_dev_cstate_frame's result record, u64 words: */
+#define PZ_CSF_STATUS           0  /* PZ_OK, PZ_EINVAL or PZ_ERANGE (as int64); with a status every other word but OFFSET is 0 */
+#define PZ_CSF_OFFSET           1  /* the violation's offset */
+#define PZ_CSF_NVAL             2  /* ValidatorRecords (field 11) */
+#define PZ_CSF_ADDRESS_BYTES    3  /* the withdrawal_address column's total */
+#define PZ_CSF_COMMITMENT_BYTES 4  /* the randao_commitment column's total */
+#define PZ_CSF_NARR             5  /* ShardAndCommitteeArrays (field 12) */
+#define PZ_CSF_NENTRIES         6  /* ShardAndCommittee entries in all of them */
+#define PZ_CSF_NMEMBERS         7  /* committee members in all of them */
+#define PZ_CSF_VAL_END          8  /* where field 11's run ends: field 12 is d_bytes[VAL_END, F12_END) */
+#define PZ_CSF_F12_END          9  /* == len */
+#define PZ_CSF_COUNT            12
+/* One ValidatorRecord (key, length, body) may take at most 512 bytes -- the offsets at which the framing
+ * lets a chain enter a tile: a body of PZ_CSTATE_RECORD_LIMIT bytes or more is PZ_ERANGE in the result
+ * record (the largest canonical record with a 20-byte address and a 32-byte commitment has 111).  The
+ * framing's units, for callers that size test inputs: a tile of 4,096 bytes, a group of 64 tiles. */
+#define PZ_CSTATE_RECORD_LIMIT 510
+#define PZ_CSTATE_TILE_BYTES   4096
+#define PZ_CSTATE_GROUP_TILES  64
+/* Device scratch of frame and decode for a message of len bytes (no reference counterpart): 2,076 bytes
+ * per tile of 4,096 (the tile tables take 2,048 of them) plus 8,204 per group of 64 tiles: below
+ * 0.54 * len + 24 KiB.  It need not be cleared. */
+uint64_t pz_cstate_scratch_bytes(uint64_t len);
+/* Frames field 11 and field 12 of d_bytes[body_beg, len) on the caller's stream, asynchronously, and
+ * sizes what decode writes: d_result[PZ_CSF_COUNT] (device).  The caller reads it back -- the load's
+ * one wait -- allocates exact-size outputs and calls pz_dev_cstate_decode with the same scratch.  A
+ * violation in a record's or an array's headers and fields is reported here; a committee member's in
+ * decode.  A message of 4 GiB or more is PZ_ERANGE in the record.  With body_beg == len (no field 11,
+ * no field 12; len == 0 included) only the record is written: zeros, both ends len.  PZ_EINVAL, before
+ * any launch: d_bytes NULL with len > 0, d_result NULL, d_scratch NULL or not 16-byte aligned,
+ * body_beg > len. */
+int pz_dev_cstate_frame(const uint8_t* d_bytes, uint64_t len, uint64_t body_beg, void* d_scratch, uint64_t* d_result,
+                        void* stream);
+/* The outputs: pz_validator_cols and pz_committee_table with pointers the decoder writes through. */
+typedef struct pz_validator_cols_out {
+  uint64_t* public_key;
+  uint64_t* withdrawal_shard;
+  uint8_t*  withdrawal_address;            /* ADDRESS_BYTES */
+  uint64_t* withdrawal_address_offs;       /* nval + 1 */
+  uint8_t*  randao_commitment;             /* COMMITMENT_BYTES */
+  uint64_t* randao_commitment_offs;        /* nval + 1 */
+  uint64_t* balance;
+  uint64_t* start_dynasty;
+  uint64_t* end_dynasty;
+} pz_validator_cols_out;
+typedef struct pz_committee_table_out {
+  uint64_t narr;                   /* the frame's NARR */
+  uint64_t* arr_offs;              /* narr + 1 */
+  uint64_t* arr_shard;             /* nentries */
+  uint32_t* arr_comm;              /* nentries: the identity, one committee per entry */
+  uint64_t ncomm;                  /* the frame's NENTRIES */
+  uint64_t* coffs;                 /* nentries + 1 */
+  uint32_t* members;               /* NMEMBERS */
+} pz_committee_table_out;
+/* Decodes what the frame found, with its scratch, on the caller's stream: every ValidatorRecord into
+ * the seven columns (a lane per record) and field 12 into the committee table (members in parallel: an
+ * element ends at each byte with a clear top bit).  d_status[2] (device): PZ_OK, or PZ_EINVAL and the
+ * offset of the first committee member that is not a minimal varint of a u32; a frame that reported a
+ * status is repeated here and nothing is written; sizes in t that are not the frame's are PZ_EINVAL at
+ * offset 0.  On error the outputs' contents are unspecified; every write lies inside the sizes the
+ * frame reported.  Every output pointer must be an address, also of an empty column.  With len == 0
+ * nothing is launched.  PZ_EINVAL, before any launch: a NULL argument or output, d_scratch not
+ * 16-byte aligned. */
+int pz_dev_cstate_decode(const uint8_t* d_bytes, uint64_t len, void* d_scratch, const pz_validator_cols_out* v,
+                         const pz_committee_table_out* t, uint64_t* d_status, void* stream);
+
 /* The stored ActiveState (messages.proto:94-97; proto.Marshal at types/state.go:141) from a
  * pz_att_pool: field 1 is pz_dev_wire_attestations over pz_att_pool_view, field 2
  * (recent_block_hashes) one lane per hash, written at the device-known end of field 1: entry i is

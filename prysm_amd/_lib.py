@@ -168,6 +168,10 @@ SIGNATURES = {
     "pz_crystallized_state_scratch_bytes": [u64],
     "pz_dev_crystallized_state_bytes": [vp, vp, vp, u64, vp, u64, vp, vp, vp, vp],
     "pz_crystallized_state_read": [vp, vp, vp, u64, vp, u64, vp, u64, c_u64p, vp],
+    "pz_cstate_head": [vp, u64, vp, vp, vp, vp, vp, vp, u64, c_u64p, c_u64p],
+    "pz_cstate_scratch_bytes": [u64],
+    "pz_dev_cstate_frame": [vp, u64, u64, vp, vp, vp],
+    "pz_dev_cstate_decode": [vp, u64, vp, vp, vp, vp, vp],
     "pz_active_state_bound": [vp, u64],
     "pz_dev_active_state_bytes": [vp, vp, vp, u64, vp, u64, vp, vp],
     "pz_active_state_read": [vp, vp, vp, u64, vp, u64, c_u64p, vp],
@@ -367,6 +371,16 @@ class CommitteeTable(ctypes.Structure):
                 ("members", vp)]
 
 
+class ValidatorColsOut(ctypes.Structure):
+    """Mirror of ``pz_validator_cols_out`` (include/prysm_hip.h)."""
+    _fields_ = ValidatorCols._fields_
+
+
+class CommitteeTableOut(ctypes.Structure):
+    """Mirror of ``pz_committee_table_out`` (include/prysm_hip.h)."""
+    _fields_ = CommitteeTable._fields_
+
+
 class CstateRest(ctypes.Structure):
     """Mirror of ``pz_cstate_rest`` (include/prysm_hip.h)."""
     _fields_ = [("crosslinking_start_shard", u64), ("dynasty_seed", ctypes.c_uint8 * 64), ("dynasty_seed_len", u32),
@@ -376,6 +390,10 @@ class CstateRest(ctypes.Structure):
 RS_LAST_STATE_RECALC, RS_JUSTIFIED_STREAK, RS_LAST_JUSTIFIED_SLOT, RS_LAST_FINALIZED_SLOT, RS_CURRENT_DYNASTY, \
     RS_TOTAL_DEPOSITS = range(6)  # pz_recalc_state's scalars
 RS_COUNT = 8
+CSF_STATUS, CSF_OFFSET, CSF_NVAL, CSF_ADDRESS_BYTES, CSF_COMMITMENT_BYTES, CSF_NARR, CSF_NENTRIES, CSF_NMEMBERS, CSF_VAL_END, \
+    CSF_F12_END = range(10)  # pz_dev_cstate_frame's result record
+CSF_COUNT = 12
+CSTATE_RECORD_LIMIT, CSTATE_TILE_BYTES, CSTATE_GROUP_TILES = 510, 4096, 64  # PZ_CSTATE_*
 SCAL_POP, SCAL_NACT, SCAL_ERR_XL, SCAL_ERR_RWD, SCAL_APPLIED, SCAL_NEXT_BAL, SCAL_MAXIDX1, SCAL_NOMATCH = range(8)
 SCAL_COUNT = 8
 KIND_ACTIVE, KIND_EXITED, KIND_QUEUED = 0, 1, 2
@@ -391,7 +409,8 @@ _RESTYPES = {"pz_last_error": ctypes.c_char_p, "pz_chain_free": None, "pz_set_se
              "pz_block_set_free": None, "pz_block_parents_scratch_bytes": u64,
              "pz_recalc_state_free": None, "pz_state_recalc_scratch_bytes": u64,
              "pz_wire_committees_bound": u64, "pz_wire_committees_scratch_bytes": u64,
-             "pz_crystallized_state_bound": u64, "pz_crystallized_state_scratch_bytes": u64, "pz_active_state_bound": u64}
+             "pz_crystallized_state_bound": u64, "pz_crystallized_state_scratch_bytes": u64, "pz_active_state_bound": u64,
+             "pz_cstate_scratch_bytes": u64}
 SERIAL_DEFAULT = 65536        # the library's default serial threshold (bytes)
 SERIAL_ON_GPU = (1 << 64) - 1  # pz_set_serial_threshold value that keeps every message on the GPU
 

@@ -873,9 +873,12 @@ class ResidentChain:
         self.cache, self.pool, self.ring, self.saved, self.state = cache, pool, ring, saved, state
         self.device = device
         dev = torch.device("cuda", device)
-        self._narr = len(shard_and_committees)
-        self._table = [_to_device(a, dev) for a in _committee_table(shard_and_committees)]
-        self._members = _to_device(_members(shard_and_committees), dev)
+        if shard_and_committees is None:  # (from_state: the table as the loader left it on the device)
+            self._narr, self._table, self._members = state.narr, list(state.table), state.members
+        else:
+            self._narr = len(shard_and_committees)
+            self._table = [_to_device(a, dev) for a in _committee_table(shard_and_committees)]
+            self._members = _to_device(_members(shard_and_committees), dev)
         self.has_candidate, self.candidate_slot, self.lag = False, 0, 0
         scal = state.read()["scalars"]
         self._cand = (int(scal[2]), int(scal[0]))  # (last_justified_slot, last_state_recalc) of the state handle
@@ -885,6 +888,23 @@ class ResidentChain:
         self.spent = False  # a call failed after its host read: the objects no longer match the carry
 
     RUN_BLOCKS = 1024  # process_all's submission: the scan's tile, and far more than a cycle's blocks of one chain
+    CAPS = (256, 256 * 32, 256 * 32, 256 * 8, 256, 256 * 32, 512)  # from_state's pool: rows and bytes of four cycles' blocks
+
+    @classmethod
+    def from_state(cls, crystallized_bytes, saved_hashes=(), device=0, slot_cap=512, caps=CAPS, hash_stride=32):
+        """NewBeaconChain over a database that holds a CrystallizedState (blockchain/core.go:86-95):
+        the state decoded on the device from its stored bytes (``ResidentRecalcState.from_state``;
+        exactly the canonical encoding is accepted), a fresh vote cache of ``slot_cap`` slots over
+        its validators, an empty pending pool of ``caps`` (``pending.CAPS``'s order), the genesis
+        ring of 128 empty entries -- the reference reloads no ActiveState (core.go:59-64) -- and the
+        saved-block set over ``saved_hashes``, the block hashes the database holds.  The committee
+        table is taken from the decoded device tensors: no validator and no member visits the host."""
+        from prysm_amd.pending import DevicePendingAttestations, DeviceRecentHashes, DeviceSavedBlocks, ResidentRecalcState
+        from prysm_amd.votes import DeviceVoteCache
+
+        state = ResidentRecalcState.from_state(crystallized_bytes, device=device, hash_stride=hash_stride)
+        return cls(DeviceVoteCache(state.nval, slot_cap, device), DevicePendingAttestations(list(caps), device),
+                   DeviceRecentHashes(device=device), DeviceSavedBlocks(list(saved_hashes), device=device), state, None, device)
 
     def chain_scalars(self):
         """``(last_justified_slot, last_state_recalc)`` of the chain's CrystallizedState: what a

@@ -467,6 +467,40 @@ class ResidentRecalcState(_DeviceValidators, _lib.Handle):
         self._new("pz_recalc_state_new", self.nrec, self.hash_stride, scalars.ctypes.data, _lib.ptr(dyn), _lib.ptr(slot),
                   _lib.ptr(data), offs.ctypes.data, device)
 
+    @classmethod
+    def from_state(cls, crystallized_bytes, device=0, hash_stride=32):
+        """NewBeaconChain's reload (blockchain/core.go:86-95) for the resident path: the state a
+        stored CrystallizedState's bytes hold, decoded on the device
+        (``wire.unwire_crystallized_state_device``: one upload, the head on the host, frame, the read
+        of its sizes, exact-size tensors, decode).  Beside ``balance / start / end / members / coffs``
+        the object carries the other ValidatorRecord columns (``public_key``, ``withdrawal_shard``,
+        ``withdrawal_address`` and ``randao_commitment`` with their ``_offs``), which
+        :meth:`validator_cols` passes on; ``rest`` (the keyword arguments of :meth:`wire` the handle
+        does not hold); ``table`` (``_committee_table``'s four arrays as device tensors) with
+        ``narr``; and ``field12``, the received span, which :meth:`wire` / :meth:`root` take as it is.
+        Exactly the canonical encoding is accepted (``PzError`` with ``.offset`` otherwise)."""
+        d = wire.unwire_crystallized_state_device(crystallized_bytes, device)
+        head = d["head"]
+        self = cls.__new__(cls)
+        self.device = device
+        self.balance, self.start, self.end = d["balance"], d["start_dynasty"], d["end_dynasty"]
+        self.members = d["members"] if d["members"].numel() else d["members"].new_zeros(1)
+        self.coffs = d["coffs"]
+        self.public_key, self.withdrawal_shard = d["public_key"], d["withdrawal_shard"]
+        self.withdrawal_address, self.withdrawal_address_offs = d["withdrawal_address"], d["withdrawal_address_offs"]
+        self.randao_commitment, self.randao_commitment_offs = d["randao_commitment"], d["randao_commitment_offs"]
+        self._val_bytes = int(d["withdrawal_address"].numel()) + int(d["randao_commitment"].numel())
+        self.table, self.narr = [d[k] for k in ("arr_offs", "arr_shard", "arr_comm", "coffs")], d["narr"]
+        self.field12 = d["field12"]
+        r = head["rest"]
+        self.rest = dict(crosslinking_start_shard=int(r.crosslinking_start_shard),
+                         dynasty_seed=bytes(r.dynasty_seed)[:r.dynasty_seed_len],
+                         dynasty_seed_last_reset=int(r.dynasty_seed_last_reset))
+        self.hash_stride, self.nrec = int(hash_stride), len(head["rec_dynasty"])
+        self._new("pz_recalc_state_new", self.nrec, self.hash_stride, head["scalars"].ctypes.data, _lib.ptr(head["rec_dynasty"]),
+                  _lib.ptr(head["rec_slot"]), _lib.ptr(head["rec_hash"]), head["rec_hash_offs"].ctypes.data, device)
+        return self
+
     def read(self, strict=True):
         """``{"scalars": uint64[8], "rec_dynasty", "rec_slot", "rec_hash" (nrec, hash_stride) uint8,
         "rec_hash_len", "winner"}`` (``pz_recalc_state_read``; waits for the last call)."""
@@ -510,9 +544,18 @@ class ResidentRecalcState(_DeviceValidators, _lib.Handle):
         return torch.from_numpy(raw.copy()).to(dev) if raw.size else torch.empty(0, dtype=torch.uint8, device=dev)
 
     def validator_cols(self):
-        """``pz_validator_cols`` over the resident balance / start / end (the other fields zero)."""
-        return _lib.ValidatorCols(balance=self.balance.data_ptr(), start_dynasty=self.start.data_ptr(),
+        """``pz_validator_cols`` over the resident balance / start / end; the other fields are the
+        columns a state loaded by :meth:`from_state` carries, and zero without them."""
+        cols = _lib.ValidatorCols(balance=self.balance.data_ptr(), start_dynasty=self.start.data_ptr(),
                                   end_dynasty=self.end.data_ptr())
+        if hasattr(self, "public_key"):
+            p = _lib.dptr
+            cols.public_key, cols.withdrawal_shard = p(self.public_key), p(self.withdrawal_shard)
+            if self.withdrawal_address.numel():
+                cols.withdrawal_address, cols.withdrawal_address_offs = p(self.withdrawal_address), p(self.withdrawal_address_offs)
+            if self.randao_commitment.numel():
+                cols.randao_commitment, cols.randao_commitment_offs = p(self.randao_commitment), p(self.randao_commitment_offs)
+        return cols
 
     def _stored(self, field12, crosslinking_start_shard, dynasty_seed, dynasty_seed_last_reset, want_root, strict):
         f12 = self._field12(field12)
@@ -522,7 +565,8 @@ class ResidentRecalcState(_DeviceValidators, _lib.Handle):
         if len(seed) <= 64:
             _lib.ctypes.memmove(rest.dynasty_seed, seed, len(seed))
         cols = self.validator_cols()
-        cap = int(lib.dll.pz_crystallized_state_bound(self.nrec, self.hash_stride, self.nval, 0, int(f12.numel())))
+        cap = int(lib.dll.pz_crystallized_state_bound(self.nrec, self.hash_stride, self.nval, getattr(self, "_val_bytes", 0),
+                                                      int(f12.numel())))
         out = np.empty(max(cap, 1), dtype=np.uint8)
         length = _lib.ctypes.c_uint64(0)
         root = np.zeros(32, dtype=np.uint8)

@@ -485,3 +485,116 @@ def committees_device(table, field_num=12, members_cap=None):
     _lib.lib.call("pz_dev_wire_committees", _lib.ctypes.byref(t), nentries, members_cap, field_num, out.data_ptr(),
                   result.data_ptr(), scr.data_ptr(), _lib.stream_ptr(dev))
     return out, result
+
+
+# ---- the stored CrystallizedState read back on the device (prysm_amd/csrc/unwire_state.hip) -------
+VALIDATOR_COLS = ("public_key", "withdrawal_shard", "withdrawal_address", "withdrawal_address_offs", "randao_commitment",
+                  "randao_commitment_offs", "balance", "start_dynasty", "end_dynasty")
+
+
+def cstate_head(raw):
+    """``pz_cstate_head`` (host only): fields 1-10 of a stored CrystallizedState.  Returns
+    ``{"scalars": uint64[8], "rest": _lib.CstateRest, "rec_dynasty", "rec_slot", "rec_hash" (uint8),
+    "rec_hash_offs" (nrec + 1), "body_beg"}``; a head that is not canonical raises ``PzError``
+    (PZ_EINVAL) with the violation's offset as ``.offset``."""
+    from prysm_amd import _lib
+
+    ct = _lib.ctypes
+    buf = np.ascontiguousarray(_lib.as_u8(raw), dtype=np.uint8)
+    scalars, rest = np.zeros(_lib.RS_COUNT, _U64), _lib.CstateRest()
+    nrec, body = ct.c_uint64(0), ct.c_uint64(0)
+    cap = 0
+    while True:
+        dyn, slot = np.zeros(max(cap, 1), _U64), np.zeros(max(cap, 1), _U64)
+        hashes, offs = np.zeros(max(buf.size, 1), np.uint8), np.zeros(cap + 1, _U64)
+        rc = _lib.lib.dll.pz_cstate_head(_lib.ptr(buf), buf.size, scalars.ctypes.data, ct.byref(rest), dyn.ctypes.data,
+                                         slot.ctypes.data, hashes.ctypes.data, offs.ctypes.data, cap, ct.byref(nrec),
+                                         ct.byref(body))
+        if rc == _lib.PZ_ERANGE and nrec.value > cap:
+            cap = nrec.value
+            continue
+        if rc != _lib.PZ_OK:
+            err = _lib.PzError(rc, _lib.lib.dll.pz_last_error().decode())
+            err.offset = body.value
+            raise err
+        n = nrec.value
+        return {"scalars": scalars, "rest": rest, "rec_dynasty": dyn[:n], "rec_slot": slot[:n], "rec_hash": hashes[:int(offs[n])],
+                "rec_hash_offs": offs, "body_beg": body.value}
+
+
+def _upload(buf, dev):
+    import warnings
+
+    import torch
+
+    with warnings.catch_warnings():  # (a read-only source, e.g. np.frombuffer: it is only copied from)
+        warnings.simplefilter("ignore", UserWarning)
+        return torch.from_numpy(buf).to(dev)
+
+
+def unwire_crystallized_state_device(raw, device=0):
+    """A stored CrystallizedState (``PersistCrystallizedState``'s bytes, blockchain/core.go:170-177)
+    loaded on the device, on the current stream: one upload of the bytes, ``pz_cstate_head`` on the
+    host, ``pz_dev_cstate_frame``, the read of its result record (the load's wait for sizes),
+    exact-size tensors, ``pz_dev_cstate_decode`` and the read of its status word.  Exactly the
+    canonical encoding is accepted: anything else raises ``PzError`` (PZ_EINVAL, or PZ_ERANGE for a
+    record over ``_lib.CSTATE_RECORD_LIMIT``) with the violation's offset as ``.offset``.
+
+    Returns the head (:func:`cstate_head`'s dict) as ``head``, ``nval``, the columns of
+    ``VALIDATOR_COLS`` and of ``TABLE_COLS`` as device tensors (int64 / int32 carrying the unsigned
+    values), ``narr`` and ``field12``: the received span of field 12, a uint8 device tensor."""
+    import torch
+
+    from prysm_amd import _lib
+
+    buf = np.ascontiguousarray(_lib.as_u8(raw), dtype=np.uint8)
+    head = cstate_head(buf)
+    dev = torch.device("cuda", device)
+    n = int(buf.size)
+    d_bytes = _upload(buf, dev) if n else torch.empty(0, dtype=torch.uint8, device=dev)  # the one upload
+    dll, sh = _lib.lib.dll, _lib.stream_ptr(dev)
+    scr = torch.empty(int(dll.pz_cstate_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+    result = torch.empty(_lib.CSF_COUNT, dtype=torch.int64, device=dev)
+    _lib.lib.call("pz_dev_cstate_frame", _lib.dptr(d_bytes), n, head["body_beg"], scr.data_ptr(), result.data_ptr(), sh)
+    r = [int(x) for x in result.cpu()]  # the wait
+
+    def refuse(status, offset):
+        err = _lib.PzError(status, "stored CrystallizedState: %s at offset %d" % (
+            "a ValidatorRecord over the framing's limit" if status == _lib.PZ_ERANGE else "not the canonical encoding", offset))
+        err.offset = offset
+        return err
+
+    if r[_lib.CSF_STATUS]:
+        raise refuse(r[_lib.CSF_STATUS], r[_lib.CSF_OFFSET])
+    nval, narr, nent, nmem = r[_lib.CSF_NVAL], r[_lib.CSF_NARR], r[_lib.CSF_NENTRIES], r[_lib.CSF_NMEMBERS]
+    size = {k: nval for k in VALIDATOR_COLS}
+    size.update(withdrawal_address=r[_lib.CSF_ADDRESS_BYTES], randao_commitment=r[_lib.CSF_COMMITMENT_BYTES],
+                withdrawal_address_offs=nval + 1, randao_commitment_offs=nval + 1, arr_offs=narr + 1, arr_shard=nent,
+                arr_comm=nent, coffs=nent + 1, members=nmem)
+    kind = {"withdrawal_address": np.uint8, "randao_commitment": np.uint8, "arr_comm": np.uint32, "members": np.uint32}
+    cols = {k: _torch_empty(torch, dev, size[k], kind.get(k, _U64)) for k in VALIDATOR_COLS + TABLE_COLS}
+    for k in ("withdrawal_address_offs", "randao_commitment_offs", "arr_offs", "coffs"):
+        cols[k][:1] = 0  # (what an empty message leaves as it is)
+    v = _lib.ValidatorColsOut(*[cols[k].data_ptr() for k in VALIDATOR_COLS])
+    t = _lib.CommitteeTableOut(narr=narr, ncomm=nent, **{k: cols[k].data_ptr() for k in TABLE_COLS})
+    status = torch.empty(2, dtype=torch.int64, device=dev)
+    _lib.lib.call("pz_dev_cstate_decode", _lib.dptr(d_bytes), n, scr.data_ptr(), _lib.ctypes.byref(v), _lib.ctypes.byref(t),
+                  status.data_ptr(), sh)
+    st = [int(x) for x in status.cpu()]
+    if st[0]:
+        raise refuse(st[0], st[1])
+    out = {k: c[:size[k]] for k, c in cols.items()}
+    out.update(head=head, nval=nval, narr=narr, field12=d_bytes[r[_lib.CSF_VAL_END]:r[_lib.CSF_F12_END]], result=r)
+    return out
+
+
+def unwire_crystallized_state(raw, device=0):
+    """:func:`unwire_crystallized_state_device` as a host-side view, for tests and tools: the same
+    dict with numpy columns (the unsigned dtypes restored) and ``field12`` as bytes."""
+    d = unwire_crystallized_state_device(raw, device)
+    out = dict(d)
+    for k in VALIDATOR_COLS + TABLE_COLS:
+        a = d[k].cpu().numpy()
+        out[k] = a.view(_U64) if a.dtype == np.int64 else a.view(np.uint32) if a.dtype == np.int32 else a
+    out["field12"] = d["field12"].cpu().numpy().tobytes()
+    return out
