@@ -839,10 +839,12 @@ int pz_vote_cache_tally(pz_vote_cache* cache, const pz_vote_cols_batch* b);
  * and totals[i] (VoteTotalDeposit) are filled when cap >= *count.  Waits for the stream of the
  * last tally.  The sticky error comes first: PZ_EINDEX where Go panics (core.go:328-329, :367),
  * else PZ_ERANGE when a call was dropped for capacity; the outputs are filled all the same (they
- * hold every call that landed). */
+ * hold every call that landed).  After a pz_[dev_]vote_cache_retain the entries are the kept ones
+ * only, in their new slot order. */
 int pz_vote_cache_read(pz_vote_cache* cache, uint8_t* hashes, uint64_t* totals, uint64_t cap, uint64_t* count);
 /* VoterIndices of one hash as a bitmap (ceil(nval / 32) u32 words, bit v & 31 of word v >> 5;
- * zeros when absent) and *present = the map has the entry.  Same waiting and errors as read. */
+ * zeros when absent) and *present = the map has the entry.  Same waiting and errors as read.  After
+ * a pz_[dev_]vote_cache_retain it speaks of the kept entries only: a dropped hash is absent. */
 int pz_vote_cache_voters(pz_vote_cache* cache, const uint8_t hash[32], uint32_t* words, int* present);
 /* `if _, ok := blockVoteCache[blockHash]` and .VoteTotalDeposit, core.go:414-418, for n hashes
  * (BytesToHash-normalised, n x 32 bytes) on the device: d_totals[q] is the entry's VoteTotalDeposit,
@@ -858,6 +860,49 @@ int pz_dev_vote_cache_lookup(pz_vote_cache* cache, const uint8_t* d_hashes, uint
  * stream of the cache's last call first. */
 int pz_vote_cache_lookup(pz_vote_cache* cache, const uint8_t* hashes, uint64_t n, uint64_t* totals,
                          uint32_t* slots /* optional */);
+/* Growth and retirement, for a chain of any length.  The reference's map (types/state.go:27-31)
+ * only grows: every candidate block's hash and every oblique parent hash becomes an entry
+ * (core.go:300-345).  A cache is created with slot_cap slots; a tally that needs more lands
+ * nothing and sets the sticky PZ_ERANGE.  Both calls below move the entries into the cache's second
+ * buffer set (allocated at the first of them, not at creation) on the device and then swap the
+ * sets; both carry the sticky error word over unchanged, are ordered on their stream like every
+ * other call on the handle, and leave lookup, read, voters, tally and pz_dev_state_recalc working
+ * on the new set.  Slots at or past the count read zero voters and a zero total, as after
+ * pz_vote_cache_new.  (votecache_dev.h holds the rules and the argument)
+ *
+ * The slots the cache holds now (no reference counterpart: a Go map has no capacity).  Host only,
+ * no device call. */
+int pz_vote_cache_capacity(pz_vote_cache* cache, uint32_t* slot_cap);
+/* Room for min_slots entries: the Go map's own growth (runtime map growth; types/state.go:27-31 has
+ * no bound).  With min_slots <= the capacity nothing happens and nothing is launched.  Otherwise
+ * the cache gets exactly min_slots slots and the cells of a cache created with as many; every entry
+ * keeps its slot id, key, total and voters.  A memset and two launches (move, rehash) on the
+ * caller's stream.  The host decides from the capacity it keeps: nothing is read back.  PZ_EINVAL,
+ * before any launch: a NULL cache, min_slots above 2^30.  An allocation failure returns PZ_EDEVICE
+ * and leaves the cache as it was. */
+int pz_dev_vote_cache_reserve(pz_vote_cache* cache, uint32_t min_slots, void* stream);
+/* The same reserve (the map's own growth, types/state.go:27-31), synchronous; waits for the stream
+ * of the cache's last call first. */
+int pz_vote_cache_reserve(pz_vote_cache* cache, uint32_t min_slots);
+/* Retirement (no reference counterpart: the Go map never deletes).  The cache keeps exactly the
+ * entries whose key is among the n hashes (n x 32 bytes, BytesToHash-normalised; a hash given twice
+ * or one the map lacks is harmless) and drops the others; a kept entry's new slot id is its rank
+ * among the kept ones in ascending old id, so ids stay deterministic; key, total and voters go
+ * with it.  n == 0 empties the cache.  The capacity stays.  What may be dropped is the caller's
+ * judgement: stateRecalc's justification loop (core.go:411-431) reads the map only at
+ * RecentBlockHashes()[0..63] of the ActiveState being promoted, and a hash that has left the ring
+ * never enters it again (service.go:320-333), so the ring's entries and the candidates of the run
+ * in hand cover every later read -- except the votes an oblique parent hash collected before the
+ * block it names became a candidate (votecache_dev.h).
+ * Two memsets and four launches (keep, renumber, move, rehash) on the caller's stream; d_scratch
+ * holds pz_vote_cache_retain_scratch_bytes(the cache's capacity, n).  PZ_EINVAL, before any launch:
+ * a NULL cache; n > 0 with a NULL d_hashes or one that is not 16-byte aligned; n >= 2^31; a NULL or
+ * misaligned d_scratch.  An allocation failure as for reserve. */
+uint64_t pz_vote_cache_retain_scratch_bytes(uint32_t slot_cap, uint64_t n);
+int pz_dev_vote_cache_retain(pz_vote_cache* cache, const uint8_t* d_hashes, uint64_t n, void* d_scratch, void* stream);
+/* The same retain (no reference counterpart) over host pointers (any alignment), synchronous;
+ * waits for the stream of the cache's last call first. */
+int pz_vote_cache_retain(pz_vote_cache* cache, const uint8_t* hashes, uint64_t n);
 
 /* ---- T/R: the block gate: which blocks go on, which rows reach the cache and the pool -----------
  * blockProcessing looks only at the LAST attestation's error (blockchain/service.go:281-306), then

@@ -117,6 +117,12 @@ SIGNATURES = {
     "pz_vote_cache_voters": [vp, vp, vp, c_intp],
     "pz_dev_vote_cache_lookup": [vp, vp, u64, vp, vp, vp],
     "pz_vote_cache_lookup": [vp, vp, u64, vp, vp],
+    "pz_vote_cache_capacity": [vp, c_u32p],
+    "pz_dev_vote_cache_reserve": [vp, u32, vp],
+    "pz_vote_cache_reserve": [vp, u32],
+    "pz_vote_cache_retain_scratch_bytes": [u32, u64],
+    "pz_dev_vote_cache_retain": [vp, vp, u64, vp, vp],
+    "pz_vote_cache_retain": [vp, vp, u64],
     "pz_dev_block_gate": [vp, vp],
     "pz_block_gate": [vp],
     "pz_recent_hashes_new": [vp, vp, u64, ctypes.c_int, vp],
@@ -402,7 +408,7 @@ _RESTYPES = {"pz_last_error": ctypes.c_char_p, "pz_chain_free": None, "pz_set_se
              "pz_wire_validators_bound": u64, "pz_wire_scratch_bytes": u64,
              "pz_wire_attestations_bound": u64, "pz_wire_attestations_scratch_bytes": u64,
              "pz_unwire_attestations_scratch_bytes": u64, "pz_unwire_blocks_scratch_bytes": u64,
-             "pz_vote_cache_free": None, "pz_vote_cache_scratch_bytes": u64,
+             "pz_vote_cache_free": None, "pz_vote_cache_scratch_bytes": u64, "pz_vote_cache_retain_scratch_bytes": u64,
              "pz_att_pool_free": None, "pz_att_pool_scratch_bytes": u64,
              "pz_recent_hashes_free": None, "pz_block_walk_scratch_bytes": u64,
              "pz_block_cycle_scratch_bytes": u64,

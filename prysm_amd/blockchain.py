@@ -589,14 +589,15 @@ def _fold_eligible(block_status, el):
     return block_status if el is None else torch.where(el != 0, block_status, torch.full_like(block_status, _INELIGIBLE))
 
 
-def _queue_run(d, nbytes, block_status, saved, result_words):
+def _queue_run(d, nbytes, block_status, saved, result_words, extra=0):
     """What a walked run queues before its scan, on the current stream, over :func:`_decode_check`'s
     tensors ``d`` (``nbytes`` of block bytes) and the folded ``block_status``: with ``saved`` (a
     ``DeviceSavedBlocks``, else None) Block.Hash, the parent check, which hands the gate a status
     that closes a block whose parent is not saved, and the gate; without it the gate, then
     Block.Hash.  It allocates the one read-back buffer, ``result | set count | flags | report | walk |
-    parent_ok`` (``result_words``: the scan's result record; the count and ``parent_ok`` only with a
-    set).  Returns a dict of device tensors: ``word`` (the buffer) with its views ``result``,
+    parent_ok | extra`` (``result_words``: the scan's result record; the count and ``parent_ok`` only with a
+    set; ``extra`` bytes of the caller's, to come along in the read).  Returns a dict of device
+    tensors: ``word`` (the buffer) with its views ``result``,
     ``flags``, ``report`` and ``walk``, ``block_hash``, the ``block_status`` the gate took,
     ``parent_ok`` (None without a set), ``vote_status`` and ``pend_take``; ``at``, the byte offset
     each part of the buffer starts at; and ``sh``, the stream."""
@@ -617,7 +618,9 @@ def _queue_run(d, nbytes, block_status, saved, result_words):
     at["report"] = at["flags"] + 4
     at["walk"] = at["report"] + n
     at["parent_ok"] = at["walk"] + n
-    word, report, vote_status, pend_take, flags = _gate(d, None, block_status, head=at["flags"], tail=n if saved is None else 2 * n)
+    at["extra"] = at["parent_ok"] + (0 if saved is None else n)
+    word, report, vote_status, pend_take, flags = _gate(d, None, block_status, head=at["flags"],
+                                                        tail=(n if saved is None else 2 * n) + extra)
     if saved is None:
         hash_blocks()
     return {"at": at, "sh": sh, "word": word, "result": word[:at["count"]].view(torch.int64), "flags": flags, "report": report,
@@ -629,12 +632,13 @@ def _read_run(q, d, saved, empty):
     """Behind the scan of :func:`_queue_run`'s ``q``: with ``saved``, ``parent_ok`` into the buffer
     (device to device: it comes along) and the walked hashes into the set, which leaves its new
     count there (``pz_dev_block_set_insert_walked``; service.go:324); then the ONE host read.
+    The caller's ``extra`` bytes come back as ``q["extra_host"]``.
     Returns ``(record, panic, out)``: the scan's result record as ints (``empty`` for a run of no
     block, which launches nothing), the gate's panic bit -- with it nothing rolled and nothing was
     inserted -- and the dict a walked run returns, so far."""
     n, at, word = d["n"], q["at"], q["word"]
     if saved is not None and n:
-        word[at["parent_ok"]:].copy_(q["parent_ok"][:n])
+        word[at["parent_ok"]:at["extra"]].copy_(q["parent_ok"][:n])
         lib.call("pz_dev_block_set_insert_walked", saved._h, _lib.dptr(q["block_hash"]), _lib.dptr(q["walk"]), _lib.dptr(q["flags"]),
                  n, word[at["count"]:].data_ptr(), q["sh"])
     host = word.cpu().numpy()  # the one read
@@ -645,7 +649,8 @@ def _read_run(q, d, saved, empty):
     out = {"walk": host[at["walk"]:at["parent_ok"]].copy(), "report": host[at["report"]:at["walk"]].copy(), "stop": record[0],
            "ncand": record[1], "has_candidate": bool(record[2]), "candidate_slot": record[3]}
     if saved is not None:
-        out["parent_ok"] = host[at["parent_ok"]:].copy()
+        out["parent_ok"] = host[at["parent_ok"]:at["extra"]].copy()
+    q["extra_host"] = host[at["extra"]:].copy()
     return record, panic, out
 
 
@@ -850,7 +855,20 @@ def resident_state_roots(pool, state, recent_hashes, field12, recent_len=None, c
 _NO_T = (1 << 64) - 1  # pz_block_cycle_batch.result's t_index without a transition block
 
 
-class ResidentChain:
+class _CachePolicyKeyword(type):
+    """``ResidentChain(..., cache_policy=...)``: the class's call takes the keyword and hands it to
+    ``_set_cache_policy`` behind ``__init__``, whose parameter list is pinned as it stands
+    (tests/test_blockcycle_abi.py)."""
+
+    def __call__(cls, *args, cache_policy="fixed", **kwargs):
+        if cache_policy not in cls.CACHE_POLICIES:  # before any object is made
+            raise PzError(_lib.PZ_EINVAL, "cache_policy %r: one of %s" % (cache_policy, ", ".join(cls.CACHE_POLICIES)))
+        self = super().__call__(*args, **kwargs)
+        self._set_cache_policy(cache_policy)
+        return self
+
+
+class ResidentChain(metaclass=_CachePolicyKeyword):
     """blockProcessing (blockchain/service.go:229-363) over the resident objects, transition blocks
     included: ``cache`` (a ``prysm_amd.votes.DeviceVoteCache``), ``pool`` (a
     ``prysm_amd.pending.DevicePendingAttestations``), ``ring`` (a ``DeviceRecentHashes``), ``saved`` (a
@@ -865,7 +883,22 @@ class ResidentChain:
     handle's.  That pair and the ring's history entry are all that tells the two pairs of states
     apart: CalculateRewards writes the balances in place (casper/incentives.go:22-28) on the slice
     stateRecalc hands to the new state (core.go:468), so the chain's old CrystallizedState tallies
-    with the rewarded balances from the transition block on."""
+    with the rewarded balances from the transition block on.
+
+    ``cache_policy``: the reference's map only grows, and a tally that needs more slots than the
+    cache has left lands nothing and sets the sticky PZ_ERANGE.  ``"fixed"`` (the default) leaves it
+    at that: the cache's ``slot_cap`` bounds the chain.  With the other two a tally never meets that
+    error.  The driver keeps an upper bound of the slots in use and, per landing, of the slots it can
+    add -- the run's hash log (the ring's 129 entries, where no earlier landing counted them, and the
+    run's candidates) plus the oblique elements of the rows that land, two sums formed on the device
+    that come along in the run's one read.  Where the bounds do not fit, ``"grow"`` reserves at least
+    the need, doubling (``DeviceVoteCache.reserve``): the map as the reference keeps it.  ``"retire"``
+    first retains the run's hash log, which already lies on the device (``DeviceVoteCache.retain``):
+    every window this call's stateRecalc and any later one can read (votecache_dev.h holds the
+    argument and what it leaves out), and reserves only if the log and the need still do not fit.
+    ``cache_retains`` and ``cache_grows`` count them."""
+
+    CACHE_POLICIES = ("fixed", "grow", "retire")
 
     def __init__(self, cache, pool, ring, saved, state, shard_and_committees, device=0):
         import torch
@@ -887,24 +920,36 @@ class ResidentChain:
         self.resubmits = 0  # of them, runs submitted again without the blocks past their stop
         self.spent = False  # a call failed after its host read: the objects no longer match the carry
 
+    def _set_cache_policy(self, cache_policy):
+        self.cache_policy = cache_policy
+        self.cache_retains = 0  # retains the policy has queued ("retire")
+        self.cache_grows = 0    # reserves that raised the capacity ("grow", "retire")
+        # host-side upper bounds, never read back: the slots in use, and whether the ring's 129 hashes
+        # are counted in it already (the landing of a run counts the run's whole log, which holds the next ring)
+        self._slots_ub = 0 if cache_policy == "fixed" else len(self.cache.read(strict=False)[1])
+        self._ring_counted = False
+
     RUN_BLOCKS = 1024  # process_all's submission: the scan's tile, and far more than a cycle's blocks of one chain
     CAPS = (256, 256 * 32, 256 * 32, 256 * 8, 256, 256 * 32, 512)  # from_state's pool: rows and bytes of four cycles' blocks
 
     @classmethod
-    def from_state(cls, crystallized_bytes, saved_hashes=(), device=0, slot_cap=512, caps=CAPS, hash_stride=32):
+    def from_state(cls, crystallized_bytes, saved_hashes=(), device=0, slot_cap=512, caps=CAPS, hash_stride=32,
+                   cache_policy="fixed"):
         """NewBeaconChain over a database that holds a CrystallizedState (blockchain/core.go:86-95):
         the state decoded on the device from its stored bytes (``ResidentRecalcState.from_state``;
         exactly the canonical encoding is accepted), a fresh vote cache of ``slot_cap`` slots over
         its validators, an empty pending pool of ``caps`` (``pending.CAPS``'s order), the genesis
         ring of 128 empty entries -- the reference reloads no ActiveState (core.go:59-64) -- and the
         saved-block set over ``saved_hashes``, the block hashes the database holds.  The committee
-        table is taken from the decoded device tensors: no validator and no member visits the host."""
+        table is taken from the decoded device tensors: no validator and no member visits the host.
+        ``cache_policy``: what a landing does when the cache's slots may not hold it (the class's text)."""
         from prysm_amd.pending import DevicePendingAttestations, DeviceRecentHashes, DeviceSavedBlocks, ResidentRecalcState
         from prysm_amd.votes import DeviceVoteCache
 
         state = ResidentRecalcState.from_state(crystallized_bytes, device=device, hash_stride=hash_stride)
         return cls(DeviceVoteCache(state.nval, slot_cap, device), DevicePendingAttestations(list(caps), device),
-                   DeviceRecentHashes(device=device), DeviceSavedBlocks(list(saved_hashes), device=device), state, None, device)
+                   DeviceRecentHashes(device=device), DeviceSavedBlocks(list(saved_hashes), device=device), state, None, device,
+                   cache_policy=cache_policy)
 
     def chain_scalars(self):
         """``(last_justified_slot, last_state_recalc)`` of the chain's CrystallizedState: what a
@@ -996,7 +1041,8 @@ class ResidentChain:
         ljs, lsr = self.chain_scalars()
         d = _decode_check(d_bytes, d_offs, n, ljs, lsr, 128, self._narr, self._table, dev, want_committee=True)
         natt, blk, status = d["natt"], d["blk"], d["status"]
-        q = _queue_run(d, nbytes, _fold_eligible(blk["status"], el), saved, 8)
+        managed = self.cache_policy != "fixed"
+        q = _queue_run(d, nbytes, _fold_eligible(blk["status"], el), saved, 8, extra=16 if managed else 0)
         p = _lib.dptr
         base = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
         log = torch.empty(int(lib.dll.pz_block_cycle_scratch_bytes(n, natt)), dtype=torch.uint8, device=dev)
@@ -1012,11 +1058,33 @@ class ResidentChain:
                                  take1=take[1].data_ptr(), walk=p(q["walk"]), base=p(base), result=p(q["result"]), log=p(log),
                                  flags=p(q["flags"]))
         lib.call("pz_dev_block_cycle", ring._h, ctypes.byref(b), q["sh"])
+        if managed and natt:  # the oblique elements of the rows each landing tallies: they come along in the read
+            nobl = d["att"]["n_oblique"][:natt]
+            lands = torch.stack([(nobl * (vote[k, :natt] == ATT_PROCESSED)).sum() for k in (0, 1)])
+            q["word"][q["at"]["extra"]:].copy_(lands.view(torch.uint8))
         empty = (0, 0, int(bool(self.has_candidate)), int(self.candidate_slot) if self.has_candidate else 0, _NO_T, 0, 0, lag)
         (_, _, has, cslot, t_index, t_rank, t_slot, lag_out), panic, out = _read_run(q, d, saved, empty)
         out["t_index"], out["lag"] = None if t_index == _NO_T else t_index, lag_out
+        nlog = 129 + out["ncand"]  # the log entries the tallies read
+        obl = [int(x) for x in np.frombuffer(q["extra_host"].tobytes(), dtype=np.uint64)] if managed else None
+        counted = [False]  # the run's log is counted in _slots_ub
+
+        def room(phase):  # before a landing's tally: the bounds fit, or the policy makes them
+            need = obl[phase] + (0 if counted[0] else nlog - (129 if self._ring_counted else 0))
+            if self._slots_ub + need > cache.slot_cap:
+                if self.cache_policy == "retire":  # the kept entries and the log's new ones are the log's hashes
+                    cache.retain(log[:32 * nlog])
+                    self.cache_retains += 1
+                    self._slots_ub, need = nlog, obl[phase]
+                if self._slots_ub + need > cache.slot_cap:
+                    cache.reserve(max(self._slots_ub + need, min(2 * cache.slot_cap, 1 << 30)), device_form=True)
+                    self.cache_grows += 1
+            self._slots_ub += need
+            counted[0] = True
 
         def land(phase):  # calculateBlockVoteCache and processedAttestations of one side of stateRecalc
+            if managed:
+                room(phase)
             cache.tally_columns(d["att"], natt, vote[phase], d["committee"], d["parents_start"], log, self._members,
                                 self._table[3], state.balance)
             pool.append_columns(d["att"], natt, status.contiguous(), d["committee"], take=take[phase])
@@ -1039,6 +1107,8 @@ class ResidentChain:
                 raise
             self.has_candidate, self.candidate_slot, self.lag = bool(has), cslot, lag_out
             self._chain = chain_pair if lag_out else None
+            # the next ring is log entries [ncand, ncand + 129): counted iff this run's log was, or nothing rolled
+            self._ring_counted = counted[0] or (self._ring_counted and out["ncand"] == 0)
         return _run_outputs(out, d, q["walk"], q["block_status"], q["block_hash"], log, want_digests), panic
 
     def process_all(self, data, offsets, eligible=None, want_digests=False):

@@ -160,7 +160,8 @@ void unstage_block_run(Stager& st, const B* hb, const B& d, uint64_t result_word
   st.down(hb->parents_start, d.parents_start, hb->natt);
 }
 
-// The vote cache's lookup side: device pointers, valid for the handle's lifetime.
+// The vote cache's lookup side: device pointers into its live buffer set, valid until the cache's
+// next reserve or retain (stream-ordered like every call on the handle).
 struct VcView {
   int device;
   uint64_t nval;

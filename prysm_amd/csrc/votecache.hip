@@ -29,6 +29,12 @@
 //
 // A lookup (the `if _, ok := blockVoteCache[blockHash]` of core.go:414-418) is one launch between
 // calls: a lane per query walks the table with votecache_dev.h's vc_probe, plain loads only.
+//
+// The reference's map only grows (types/state.go:27-31).  pz_[dev_]vote_cache_reserve gives the
+// cache more slots and pz_[dev_]vote_cache_retain keeps only the entries a caller names; both move
+// the entries into the handle's second buffer set, allocated at the first such call, and swap the
+// sets (keep, renumber, move, rehash below; the rules and the retirement argument are
+// votecache_dev.h's).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -38,16 +44,23 @@
 
 #include "att_cols.h"
 #include "resident.h"
+#include "tile_scan.h"
 #include "votecache_dev.h"
 #include "votes_dev.h"
 
 struct pz_vote_cache : pz::Resident {  // (last: read / voters / the host forms wait for it)
   uint64_t nval = 0, words = 0;
   uint32_t slot_cap = 0, cells = 0;
-  pz::DevBuf bitmaps, totals, keys, table, words2;  // words2: nslots (u32) at 0, the error word (u64) at 8
+  // Two buffer sets: set `live` is the map; the other one, allocated at the first reserve or retain,
+  // is where that call moves the entries to before the sets swap (the pool's prune, the block set's
+  // reserve).  words2: nslots (u32) at 0, the error word (u64) at 8 -- one pair for both sets.
+  pz::DevBuf bitmaps[2], totals[2], keys[2], table[2], words2;
+  int live = 0;
   ~pz_vote_cache() {
     drain();
-    for (pz::DevBuf* b : {&bitmaps, &totals, &keys, &table, &words2}) b->release();
+    for (int k = 0; k < 2; ++k)
+      for (pz::DevBuf* b : {&bitmaps[k], &totals[k], &keys[k], &table[k]}) b->release();
+    words2.release();
   }
 };
 
@@ -285,6 +298,121 @@ extern "C" __global__ void __launch_bounds__(kThreads) pz_vc_lookup_kernel(VcLoo
   if (a.out_slots) a.out_slots[q] = slot;
 }
 
+// ---- reserve and retain: the entries move to the other buffer set ------------------------------
+// A reserve is a memset of the new table and two launches (move, rehash); a retain puts a memset of
+// the flags and two launches in front (keep, renumber).  Every fact crosses a launch boundary: the
+// flags keep -> renumber, new nslots and old_of renumber -> move, the moved keys move -> rehash.
+struct VcSet {
+  uint32_t* bitmaps;
+  uint64_t* totals;
+  uint8_t* keys;
+  uint32_t* table;
+  uint32_t slot_cap, cells;
+};
+
+struct VcMoveArgs {
+  VcSet from, to;
+  uint32_t* nslots;  // the cache's count: the old one up to renumber, the new one after it
+  uint64_t* err;
+  uint64_t words;
+  uint64_t per_row;  // move: lanes a destination row
+  // a retain's scratch and keep-hashes (a reserve: NULL, every slot keeps its id)
+  uint32_t* flag;
+  uint32_t* new_id;
+  uint32_t* old_of;
+  const uint8_t* hashes;  // n x 32 B, 16-byte aligned
+  uint64_t n;
+};
+
+__device__ __forceinline__ uint32_t vc_count(const uint32_t* nslots, uint32_t slot_cap) {
+  const uint32_t ns = *nslots;
+  return ns < slot_cap ? ns : slot_cap;
+}
+
+// keep: a lane per keep-hash.  Lanes that find the same slot store the same word.
+extern "C" __global__ void __launch_bounds__(kThreads) pz_vc_keep_kernel(VcMoveArgs a) {
+  const uint64_t q = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (q >= a.n) return;
+  const uint32_t ns = vc_count(a.nslots, a.from.slot_cap);
+  const uint32_t slot = vc_keep_mark(a.from.table, a.from.cells, a.from.keys, ns, vc_load_hash16(a.hashes + 32 * q));
+  if (slot != kVcNone) a.flag[slot] = 1;
+}
+
+// renumber: ONE workgroup scans the flags a tile (tile_scan.h) at a time: new_id[old], old_of[new]
+// for the move, and the new count into the cache's word.
+extern "C" __global__ void __launch_bounds__(kTile) pz_vc_renumber_kernel(VcMoveArgs a) {
+  __shared__ uint64_t s_tile;
+  const uint32_t ns = vc_count(a.nslots, a.from.slot_cap);
+  __syncthreads();  // every lane has read the old count before lane 0 writes the new one
+  uint64_t kept_before = 0;
+  for (uint64_t s0 = 0; s0 < ns; s0 += kTile) {  // (block-uniform)
+    const uint64_t s = s0 + threadIdx.x;
+    const bool kept = vc_kept(a.flag, ns, s);
+    const uint64_t v[1] = {kept ? 1ull : 0ull};
+    uint64_t ex[1];
+    tile_excl<1>(v, ex);
+    if (threadIdx.x == kTile - 1) s_tile = ex[0] + v[0];
+    const uint32_t id = vc_new_id(kept, kept_before + ex[0]);
+    if (s < ns) a.new_id[s] = id;
+    if (kept) a.old_of[id] = (uint32_t)s;
+    __syncthreads();
+    kept_before += s_tile;
+    __syncthreads();  // (s_tile and tile_excl's sums are read: the next tile may write them)
+  }
+  if (threadIdx.x == 0) *a.nslots = (uint32_t)kept_before;
+}
+
+// move: per_row lanes a destination row d of the new set, every row of it: below the new count the
+// row of slot old_of[d] (a reserve: d), at or past it zeros -- the other set may hold an earlier
+// swap's rows, and the tally counts on fresh slots reading zero.  Lane i moves 16-byte piece i of
+// the voters (aligned stores; the source row may start at another dword: unaligned loads, which
+// gfx950 runs); lane 0 also moves the head and tail dwords, the key and the total.
+extern "C" __global__ void __launch_bounds__(kThreads) pz_vc_move_kernel(VcMoveArgs a) {
+  const uint64_t g = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  const uint64_t d = g / a.per_row, i = g - d * a.per_row;
+  if (d >= a.to.slot_cap) return;
+  const uint32_t ns = vc_count(a.nslots, a.to.slot_cap);
+  uint64_t o = 0;
+  bool live = d < ns;
+  if (live) {
+    o = a.old_of ? a.old_of[d] : d;
+    live = o < a.from.slot_cap;  // (always: old_of holds old slot ids)
+    if (!live) o = 0;
+  }
+  const uint64_t w = a.words;
+  uint32_t* dst = a.to.bitmaps + d * w;
+  const uint32_t* src = a.from.bitmaps + o * w;
+  const uint32_t head = vc_row_head(d * w, w);
+  const uint64_t pieces = (w - head) / 4;
+  if (i < pieces) {
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (live) __builtin_memcpy(&v, src + head + 4 * i, 16);
+    *reinterpret_cast<uint4*>(__builtin_assume_aligned(dst + head + 4 * i, 16)) = v;
+  }
+  if (i != 0) return;
+  for (uint64_t k = 0; k < head; ++k) dst[k] = live ? src[k] : 0;
+  for (uint64_t k = head + 4 * pieces; k < w; ++k) dst[k] = live ? src[k] : 0;
+  a.to.totals[d] = live ? a.from.totals[o] : 0;
+  uint4 k0 = make_uint4(0, 0, 0, 0), k1 = k0;
+  if (live) {
+    const uint4* fk = reinterpret_cast<const uint4*>(a.from.keys + 32 * o);
+    k0 = fk[0], k1 = fk[1];
+  }
+  uint4* tk = reinterpret_cast<uint4*>(a.to.keys + 32 * d);
+  tk[0] = k0, tk[1] = k1;
+}
+
+// rehash: a lane per slot of the new set claims the first empty cell of its key's probe in the new
+// table (cleared by the memset before the move); only atomics touch a cell.
+extern "C" __global__ void __launch_bounds__(kThreads) pz_vc_rehash_kernel(VcMoveArgs a) {
+  const uint64_t s = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (s >= vc_count(a.nslots, a.to.slot_cap)) return;
+  const Hash32 h = vc_load_hash16(a.to.keys + 32 * s);
+  uint32_t* table = a.to.table;
+  const uint32_t cell = vc_rehash_insert(a.to.cells, h, [table, s](uint32_t c) { return atomicCAS(&table[c], kVcEmpty, (uint32_t)s) == kVcEmpty; });
+  if (cell == kVcNone) atomicOr((unsigned long long*)a.err, (unsigned long long)kVcErrCapacity);  // (cells >= 2 * slots: unreachable)
+}
+
 // ---- host side ---------------------------------------------------------------------------------
 // What can be told without reading a column; 1: nothing to do.
 int check_args(const pz_vote_cache* h, const pz_vote_cols_batch* b) {
@@ -315,10 +443,10 @@ int enqueue(pz_vote_cache* h, const pz_vote_cols_batch& b, void* d_scratch, hipS
   VcArgs a;
   std::memset(&a, 0, sizeof a);
   a.b = b;
-  a.bitmaps = static_cast<uint32_t*>(h->bitmaps.ptr);
-  a.totals = static_cast<uint64_t*>(h->totals.ptr);
-  a.keys = static_cast<uint8_t*>(h->keys.ptr);
-  a.table = static_cast<uint32_t*>(h->table.ptr);
+  a.bitmaps = static_cast<uint32_t*>(h->bitmaps[h->live].ptr);
+  a.totals = static_cast<uint64_t*>(h->totals[h->live].ptr);
+  a.keys = static_cast<uint8_t*>(h->keys[h->live].ptr);
+  a.table = static_cast<uint32_t*>(h->table[h->live].ptr);
   a.nslots = static_cast<uint32_t*>(h->words2.ptr);
   a.err = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(h->words2.ptr) + 8);
   a.nval = h->nval, a.words = h->words, a.slot_cap = h->slot_cap, a.cells = h->cells;
@@ -382,16 +510,92 @@ int enqueue_lookup(pz_vote_cache* h, const uint8_t* d_hashes, uint64_t n, uint64
                    hipStream_t s) {
   if (!aligned16(d_hashes)) return fail(PZ_EINVAL, "lookup: hashes must be 16-B aligned");
   VcLookupArgs a;
-  a.table = static_cast<const uint32_t*>(h->table.ptr);
-  a.keys = static_cast<const uint8_t*>(h->keys.ptr);
+  a.table = static_cast<const uint32_t*>(h->table[h->live].ptr);
+  a.keys = static_cast<const uint8_t*>(h->keys[h->live].ptr);
   a.nslots = static_cast<const uint32_t*>(h->words2.ptr);
-  a.totals = static_cast<const uint64_t*>(h->totals.ptr);
+  a.totals = static_cast<const uint64_t*>(h->totals[h->live].ptr);
   a.slot_cap = h->slot_cap, a.cells = h->cells;
   a.hashes = d_hashes, a.n = n, a.out_totals = d_totals, a.out_slots = d_slots;
   h->last = s;
   hipLaunchKernelGGL(pz_vc_lookup_kernel, dim3((uint32_t)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? PZ_OK : hip_fail(e, "pz_vc_lookup_kernel");
+}
+
+// ---- reserve and retain, host side ---------------------------------------------------------------
+VcSet set_of(pz_vote_cache* h, int which, uint32_t slot_cap, uint32_t cells) {
+  return VcSet{static_cast<uint32_t*>(h->bitmaps[which].ptr), static_cast<uint64_t*>(h->totals[which].ptr),
+               static_cast<uint8_t*>(h->keys[which].ptr), static_cast<uint32_t*>(h->table[which].ptr), slot_cap, cells};
+}
+
+uint64_t retain_scratch_bytes(uint32_t slot_cap) { return 3 * r16(4ull * slot_cap); }  // flag | new_id | old_of
+
+int check_reserve(const pz_vote_cache* h, uint32_t min_slots) {
+  if (!h) return fail(PZ_EINVAL, "vote cache is null");
+  if (min_slots > kVcMaxSlotCap) return fail(PZ_EINVAL, "a vote cache of %u slots: above 2^30", min_slots);
+  return PZ_OK;
+}
+
+int check_retain(const pz_vote_cache* h, const uint8_t* hashes, uint64_t n) {
+  if (!h) return fail(PZ_EINVAL, "vote cache is null");
+  if (n >= (1ull << 31)) return fail(PZ_EINVAL, "retain: n %llu: 2^31 hashes or more", (unsigned long long)n);
+  if (n && !hashes) return fail(PZ_EINVAL, "retain: null hashes");
+  return PZ_OK;
+}
+
+// The entries into the other buffer set, of new_cap slots, on s; then the sets swap.  retain: only
+// the entries whose key is among the n hashes, renumbered (d_scratch: retain_scratch_bytes of the
+// cache's slot_cap); else every entry where it was.  An allocation failure leaves the cache as it
+// was.  ev (the A/B library's timed entry): seven events around the six steps, a reserve from 3 on.
+int enqueue_move(pz_vote_cache* h, uint32_t new_cap, bool retain, const uint8_t* d_hashes, uint64_t n, void* d_scratch,
+                 hipStream_t s, Events* ev = nullptr) {
+  const uint32_t new_cells = vc_cells(new_cap);
+  const int other = h->live ^ 1;
+  VcMoveArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.words = h->words;
+  a.per_row = h->words / 4 + 1;
+  const uint64_t move_blocks = ((uint64_t)new_cap * a.per_row + kThreads - 1) / kThreads;
+  if (move_blocks >= (1ull << 31)) return fail(PZ_EINVAL, "a vote cache of %u slots of %llu words: too large to move", new_cap, (unsigned long long)h->words);
+  int rc;
+  if ((rc = h->bitmaps[other].reserve((size_t)new_cap * h->words * 4)) || (rc = h->totals[other].reserve((size_t)new_cap * 8)) ||
+      (rc = h->keys[other].reserve((size_t)new_cap * 32)) || (rc = h->table[other].reserve((size_t)new_cells * 4)))
+    return rc;
+  a.from = set_of(h, h->live, h->slot_cap, h->cells);
+  a.to = set_of(h, other, new_cap, new_cells);
+  a.nslots = static_cast<uint32_t*>(h->words2.ptr);
+  a.err = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(h->words2.ptr) + 8);
+  hipError_t e;
+  h->last = s;
+  if (retain) {
+    uint8_t* p = static_cast<uint8_t*>(d_scratch);
+    const uint64_t part = r16(4ull * h->slot_cap);
+    a.flag = reinterpret_cast<uint32_t*>(p);
+    a.new_id = reinterpret_cast<uint32_t*>(p + part);
+    a.old_of = reinterpret_cast<uint32_t*>(p + 2 * part);
+    a.hashes = d_hashes, a.n = n;
+    stamp(ev, 0, s);
+    if ((e = hipMemsetAsync(a.flag, 0, part, s)) != hipSuccess) return hip_fail(e, "hipMemsetAsync");
+    stamp(ev, 1, s);
+    if (n) {
+      hipLaunchKernelGGL(pz_vc_keep_kernel, dim3((uint32_t)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
+      if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_vc_keep_kernel");
+    }
+    stamp(ev, 2, s);
+    hipLaunchKernelGGL(pz_vc_renumber_kernel, dim3(1), dim3(kTile), 0, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_vc_renumber_kernel");
+  }
+  stamp(ev, 3, s);
+  if ((e = hipMemsetAsync(a.to.table, 0xFF, (size_t)new_cells * 4, s)) != hipSuccess) return hip_fail(e, "hipMemsetAsync");
+  stamp(ev, 4, s);
+  hipLaunchKernelGGL(pz_vc_move_kernel, dim3((uint32_t)move_blocks), dim3(kThreads), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_vc_move_kernel");
+  stamp(ev, 5, s);
+  hipLaunchKernelGGL(pz_vc_rehash_kernel, dim3((new_cap + kThreads - 1) / kThreads), dim3(kThreads), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_vc_rehash_kernel");
+  stamp(ev, 6, s);
+  h->live = other, h->slot_cap = new_cap, h->cells = new_cells;
+  return PZ_OK;
 }
 
 }  // namespace
@@ -402,10 +606,10 @@ int vote_cache_view(pz_vote_cache* h, VcView* v, hipStream_t s) {
   v->device = h->device;
   v->nval = h->nval;
   v->slot_cap = h->slot_cap, v->cells = h->cells;
-  v->table = static_cast<const uint32_t*>(h->table.ptr);
-  v->keys = static_cast<const uint8_t*>(h->keys.ptr);
+  v->table = static_cast<const uint32_t*>(h->table[h->live].ptr);
+  v->keys = static_cast<const uint8_t*>(h->keys[h->live].ptr);
   v->nslots = static_cast<const uint32_t*>(h->words2.ptr);
-  v->totals = static_cast<const uint64_t*>(h->totals.ptr);
+  v->totals = static_cast<const uint64_t*>(h->totals[h->live].ptr);
   h->last = s;
   return PZ_OK;
 }
@@ -458,8 +662,8 @@ int pz_vote_cache_new(uint64_t nval, uint32_t slot_cap, int device, pz_vote_cach
   h->cells = vc_cells(slot_cap);
   const size_t bm = (size_t)slot_cap * h->words * 4;
   const char* what = "vote cache init";
-  if ((rc = h->bitmaps.fill(bm, 0, what)) || (rc = h->totals.fill((size_t)slot_cap * 8, 0, what)) ||
-      (rc = h->keys.fill((size_t)slot_cap * 32, 0, what)) || (rc = h->table.fill((size_t)h->cells * 4, 0xFF, what)) ||
+  if ((rc = h->bitmaps[0].fill(bm, 0, what)) || (rc = h->totals[0].fill((size_t)slot_cap * 8, 0, what)) ||
+      (rc = h->keys[0].fill((size_t)slot_cap * 32, 0, what)) || (rc = h->table[0].fill((size_t)h->cells * 4, 0xFF, what)) ||
       (rc = h->words2.fill(16, 0, what)) || ((e = hipDeviceSynchronize()) != hipSuccess && (rc = hip_fail(e, what)))) {
     delete h;
     return rc;
@@ -536,6 +740,82 @@ int pz_vote_cache_tally(pz_vote_cache* h, const pz_vote_cols_batch* hb) {
   return st.sync();
 }
 
+int pz_vote_cache_capacity(pz_vote_cache* h, uint32_t* slot_cap) {
+  if (!h || !slot_cap) return fail(PZ_EINVAL, "vote cache / slot_cap is null");
+  std::lock_guard<std::mutex> lk(h->mu);
+  *slot_cap = h->slot_cap;
+  return PZ_OK;
+}
+
+int pz_dev_vote_cache_reserve(pz_vote_cache* h, uint32_t min_slots, void* stream) {
+  int rc = check_reserve(h, min_slots);
+  if (rc) return rc;
+  if ((rc = h->use())) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (min_slots <= h->slot_cap) return PZ_OK;
+  return enqueue_move(h, min_slots, false, nullptr, 0, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int pz_vote_cache_reserve(pz_vote_cache* h, uint32_t min_slots) {
+  int rc = check_reserve(h, min_slots);
+  if (rc) return rc;
+  HostForm f(h, "vote cache reserve");
+  if (f.rc) return f.rc;
+  if (min_slots <= h->slot_cap) return PZ_OK;
+  if ((rc = enqueue_move(h, min_slots, false, nullptr, 0, nullptr, f.st.s))) return rc;
+  return f.st.sync();
+}
+
+uint64_t pz_vote_cache_retain_scratch_bytes(uint32_t slot_cap, uint64_t n) {
+  (void)n;  // (the keep-hashes are read where they lie)
+  return retain_scratch_bytes(slot_cap);
+}
+
+int pz_dev_vote_cache_retain(pz_vote_cache* h, const uint8_t* d_hashes, uint64_t n, void* d_scratch, void* stream) {
+  int rc = check_retain(h, d_hashes, n);
+  if (rc) return rc;
+  if (n && !aligned16(d_hashes)) return fail(PZ_EINVAL, "retain: hashes must be a 16-B aligned device pointer");
+  if (!d_scratch || !aligned16(d_scratch)) return fail(PZ_EINVAL, "d_scratch must be a 16-B aligned device pointer");
+  if ((rc = h->use())) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  return enqueue_move(h, h->slot_cap, true, d_hashes, n, d_scratch, static_cast<hipStream_t>(stream));
+}
+
+int pz_vote_cache_retain(pz_vote_cache* h, const uint8_t* hashes, uint64_t n) {
+  int rc = check_retain(h, hashes, n);
+  if (rc) return rc;
+  HostForm f(h, "vote cache retain");
+  if (f.rc) return f.rc;
+  Stager& st = f.st;
+  const uint8_t* d_hashes = n ? st.up(hashes, n * 32) : nullptr;
+  uint8_t* scr = st.up<uint8_t>(nullptr, retain_scratch_bytes(h->slot_cap));
+  if (st.rc) return st.rc;
+  if ((rc = enqueue_move(h, h->slot_cap, true, d_hashes, n, scr, st.s))) return rc;
+  return st.sync();
+}
+
+#ifdef PZ_AB_BUILD
+// (tools/votecache_retain_probe.py) pz_dev_vote_cache_retain (retain != 0) or pz_dev_vote_cache_reserve
+// with one event pair per step; synchronises and returns the steps' milliseconds in ms[0..6): the
+// flags' memset, keep, renumber (a reserve: zeros), the table's memset, move, rehash.
+int pz_debug_vote_cache_move_timed(pz_vote_cache* h, uint32_t min_slots, int retain, const uint8_t* d_hashes, uint64_t n,
+                                   void* d_scratch, void* stream, float ms[6]) {
+  int rc = retain ? check_retain(h, d_hashes, n) : check_reserve(h, min_slots);
+  if (rc) return rc;
+  if (!ms || (retain && !d_scratch) || (!retain && min_slots <= h->slot_cap)) return fail(PZ_EINVAL, "timed move: nothing to time");
+  if ((rc = h->use())) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  Events ev;
+  if ((rc = ev.create(7))) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int k = 0; k < 6; ++k) ms[k] = 0;
+  rc = enqueue_move(h, retain ? h->slot_cap : min_slots, retain != 0, d_hashes, n, d_scratch, s, &ev);
+  const int first = retain ? 0 : 3;
+  static const int pairs[6] = {0, 1, 2, 3, 4, 5};
+  return ev.elapsed(rc, ms + first, pairs + first, 6 - first, s, "timed vote cache move");
+}
+#endif
+
 int pz_vote_cache_read(pz_vote_cache* h, uint8_t* hashes, uint64_t* totals, uint64_t cap, uint64_t* count) {
   if (!h || !count) return fail(PZ_EINVAL, "vote cache / count is null");
   int rc = h->use();
@@ -547,8 +827,8 @@ int pz_vote_cache_read(pz_vote_cache* h, uint8_t* hashes, uint64_t* totals, uint
   *count = ns;
   if (ns && cap >= ns) {
     hipError_t e = hipSuccess;
-    if (hashes) e = hipMemcpy(hashes, h->keys.ptr, (size_t)ns * 32, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && totals) e = hipMemcpy(totals, h->totals.ptr, (size_t)ns * 8, hipMemcpyDeviceToHost);
+    if (hashes) e = hipMemcpy(hashes, h->keys[h->live].ptr, (size_t)ns * 32, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && totals) e = hipMemcpy(totals, h->totals[h->live].ptr, (size_t)ns * 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "vote cache read");
   }
   return report(sticky);
@@ -564,7 +844,7 @@ int pz_vote_cache_voters(pz_vote_cache* h, const uint8_t hash[32], uint32_t* wor
   if ((rc = settle(h, &ns, &sticky))) return rc;
   // (a read-side lookup: the keys come to the host; the tally never does this)
   std::vector<uint8_t> keys((size_t)ns * 32);
-  hipError_t e = ns ? hipMemcpy(keys.data(), h->keys.ptr, keys.size(), hipMemcpyDeviceToHost) : hipSuccess;
+  hipError_t e = ns ? hipMemcpy(keys.data(), h->keys[h->live].ptr, keys.size(), hipMemcpyDeviceToHost) : hipSuccess;
   if (e != hipSuccess) return hip_fail(e, "vote cache voters");
   *present = 0;
   uint32_t slot = 0;
@@ -572,7 +852,7 @@ int pz_vote_cache_voters(pz_vote_cache* h, const uint8_t hash[32], uint32_t* wor
     if (!std::memcmp(keys.data() + 32ull * slot, hash, 32)) break;
   if (slot < ns) {
     *present = 1;
-    if (words) e = hipMemcpy(words, static_cast<uint32_t*>(h->bitmaps.ptr) + (size_t)slot * h->words, h->words * 4, hipMemcpyDeviceToHost);
+    if (words) e = hipMemcpy(words, static_cast<uint32_t*>(h->bitmaps[h->live].ptr) + (size_t)slot * h->words, h->words * 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "vote cache voters");
   } else if (words) {
     std::memset(words, 0, h->words * 4);

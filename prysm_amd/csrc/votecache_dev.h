@@ -2,8 +2,10 @@
 // the hash-to-slot table's cell encodings, home cell and probe step, common.BytesToHash from a
 // byte range, the oblique skip rule of calculateBlockVoteCache (blockchain/core.go:300-345) and
 // the place of a signed parent hash (getSignedParentHashes, core.go:348-360) among a call's
-// sources.  The kernels and the stand-alone CPU check (tests/votecache_san.cpp, plain g++ under
-// ASan+UBSan) compile the same text.
+// sources, and the rules of its growth and retirement (the keep decision, the renumbering, the
+// rehash insert, with the argument for which entries may be retired).  The kernels and the
+// stand-alone CPU checks (tests/votecache_san.cpp, tests/votecache_retain_san.cpp, plain g++
+// under ASan+UBSan) compile the same text.
 #pragma once
 #include <stdint.h>
 
@@ -127,6 +129,63 @@ PZ_HD bool vc_parents_in_range(uint64_t m, uint64_t ps, uint64_t n_recent) {
 PZ_HD uint64_t vc_parent_source(uint32_t r, uint64_t m, uint64_t ps, uint64_t f0, uint64_t n_recent) {
   const uint64_t nrec = kVcParents - m;
   return r < nrec ? ps + r : n_recent + f0 + (r - nrec);
+}
+
+// ---- growth and retirement (pz_[dev_]vote_cache_reserve, pz_[dev_]vote_cache_retain) ---------
+// The reference's map only grows (types/state.go:27-31): every candidate block's hash and every
+// oblique parent hash becomes an entry (core.go:300-345) and none is ever deleted.  A reserve
+// keeps that meaning exactly: more slots, every entry where it was.  A retain keeps the entries
+// whose key is among the caller's hashes and drops the rest.
+//
+// Which entries a later stateRecalc can still read.  The justification loop (core.go:411-431)
+// reads blockVoteCache only at RecentBlockHashes()[0..63] of the ActiveState being promoted; the
+// map is part of neither state's encoding nor root and is not persisted.  RecentBlockHashes is a
+// window of 128 candidate hashes that moves on by one whenever a block replaces the candidate, and
+// a candidate is only ever replaced by a block of a strictly higher slot (service.go:320-333): a
+// block hash that has left the ring never enters it again.  So an entry whose key is neither in
+// the ring (its 128 entries and the one hash of history beside them) nor among the candidates of
+// the run in hand -- the run's hash log, every window any block of the run or any later block can
+// name -- is read by no later justification loop: a later tally may create it anew (an oblique
+// parent of that hash), but no loop asks for it.
+// What the argument does NOT cover: a hash that is voted for as an OBLIQUE parent before the block
+// it names becomes a candidate.  The reference keeps those votes until the hash enters the ring; a
+// retain between the vote and the block's arrival drops them.  Retirement is therefore a caller's
+// choice (prysm_amd.blockchain.ResidentChain cache_policy="retire"), never the default; growth
+// alone ("grow") is exact.
+//
+// The rules, shared by the kernels of votecache.hip and tests/votecache_retain_san.cpp:
+//   keep      a keep-hash marks the slot its probe finds (vc_keep_mark: vc_probe's answer; an
+//             absent hash marks nothing, a hash given twice marks the same slot twice);
+//   renumber  a kept slot's new id is its rank among the kept slots in ascending old id
+//             (vc_new_id over the exclusive count of kept flags before it), a dropped slot's is
+//             kVcDropped: slot ids stay deterministic;
+//   rehash    the kept keys are distinct, so the first empty cell of a key's probe is claimed
+//             without comparing keys (vc_rehash_insert; the claim is an atomicCAS on the device).
+constexpr uint32_t kVcDropped = 0xFFFFFFFFu;  // new_id of a slot the retain drops
+
+PZ_HD uint32_t vc_keep_mark(const uint32_t* table, uint32_t cells, const uint8_t* keys, uint32_t nslots, const Hash32& h) {
+  return vc_probe(table, cells, keys, nslots, h);
+}
+PZ_HD bool vc_kept(const uint32_t* flag, uint32_t nslots, uint64_t slot) { return slot < nslots && flag[slot] != 0; }
+PZ_HD uint32_t vc_new_id(bool kept, uint64_t kept_before) { return kept ? (uint32_t)kept_before : kVcDropped; }
+
+// claim(cell): true iff the cell was empty and now holds the key's slot.  Linear probing with
+// wraparound from the home cell, at most `cells` steps; the cell taken, or kVcNone when every
+// cell is full (cells >= 2 * slots: unreachable).
+template <class Claim>
+PZ_HD uint32_t vc_rehash_insert(uint32_t cells, const Hash32& h, Claim claim) {
+  uint32_t c = vc_home(h, cells);
+  for (uint32_t step = 0; step < cells; ++step, c = vc_next(c, cells))
+    if (claim(c)) return c;
+  return kVcNone;
+}
+
+// The move of one voter row (`words` u32) between buffer sets whose rows start at any dword: the
+// destination is written in 16-byte pieces where it is 16-byte aligned, so a row splits into a head
+// of vc_row_head dwords, (words - head) / 4 pieces and a tail of (words - head) % 4 dwords.
+PZ_HD uint32_t vc_row_head(uint64_t first_dword, uint64_t words) {
+  const uint64_t h = (4 - (first_dword & 3)) & 3;
+  return (uint32_t)(h < words ? h : words);
 }
 
 // The sticky error word's bits.

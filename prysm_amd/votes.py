@@ -146,6 +146,43 @@ class DeviceVoteCache(_lib.Handle):
                         **{k: v.ctypes.data for k, v in keep.items() if v is not None and v.size})
         lib.call("pz_vote_cache_tally", self._h, _lib.ctypes.byref(b))
 
+    def _capacity(self):
+        cap = _lib.ctypes.c_uint32(0)
+        lib.call("pz_vote_cache_capacity", self._h, _lib.ctypes.byref(cap))
+        self.slot_cap = int(cap.value)
+        return self.slot_cap
+
+    def reserve(self, min_slots, device_form=False):
+        """Room for ``min_slots`` entries, the Go map's own growth (``pz_[dev_]vote_cache_reserve``;
+        ``device_form``: on the current stream, asynchronous): every entry keeps its slot id, key,
+        total and voters; at or below the capacity nothing is launched.  ``slot_cap`` follows the
+        handle.  Returns the capacity."""
+        if device_form:
+            lib.call("pz_dev_vote_cache_reserve", self._h, int(min_slots), _lib.stream_ptr(self.device))
+        else:
+            lib.call("pz_vote_cache_reserve", self._h, int(min_slots))
+        return self._capacity()
+
+    def retain(self, hashes):
+        """Keeps exactly the entries whose key is among ``hashes`` and renumbers them by ascending
+        old slot id; no hash empties the cache.  A device tensor ((k, 32) uint8, 16-byte aligned)
+        takes ``pz_dev_vote_cache_retain`` on the current stream, asynchronous; a list of byte strings
+        or a (k, 32) uint8 array takes ``pz_vote_cache_retain``, synchronous.  What may be dropped is
+        the caller's judgement (include/prysm_hip.h): the reference's map never forgets."""
+        if hasattr(hashes, "data_ptr"):
+            import torch
+
+            n = int(hashes.numel()) // 32
+            nbytes = int(lib.dll.pz_vote_cache_retain_scratch_bytes(self.slot_cap, n))
+            scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=hashes.device)  # (reused in stream order)
+            lib.call("pz_dev_vote_cache_retain", self._h, _lib.dptr(hashes), n, scratch.data_ptr(), _lib.stream_ptr(hashes.device))
+            return
+        if isinstance(hashes, np.ndarray):
+            q = np.ascontiguousarray(hashes, dtype=np.uint8).reshape(-1, 32)
+        else:
+            q = np.frombuffer(b"".join(bytes(h) for h in hashes), dtype=np.uint8).reshape(-1, 32)
+        lib.call("pz_vote_cache_retain", self._h, ptr(q), len(q))
+
     def read(self, strict=True):
         """``(hashes (k, 32) uint8, totals (k) uint64)`` in slot order (``pz_vote_cache_read``)."""
         cnt = _lib.ctypes.c_uint64(0)
