@@ -694,7 +694,19 @@ int  pz_epoch_plan(const pz_epoch_host* h, int world, int rank, uint64_t* lo, ui
  * check that failed (PZ_ATT_*), or PZ_ERANGE / PZ_EINDEX where Go panics (the slice bounds
  * of :353, the committee index of :367).  committee[i] (optional) receives the committee id
  * (UINT32_MAX if not reached) and parents_start[i] (optional) the first RecentBlockHashes
- * index the signed parent hashes start at. */
+ * index the signed parent hashes start at.
+ * What tests/test_attcheck_dev_gpu.py pins, for both entry points and every kernel form:
+ *  - a row that does not reach the committee walk (PZ_ATT_SLOT_HIGH, _SLOT_LOW, _JUSTIFIED,
+ *    PZ_ERANGE, PZ_EINDEX) gets committee UINT32_MAX and parents_start 0; PZ_ATT_NO_COMMITTEE
+ *    gets UINT32_MAX and block_slot - slot; every later status the committee id and
+ *    block_slot - slot (the block gate completes these two columns in place);
+ *  - last_byte, when given, is the only source of the trailing-bits byte: bits is not read;
+ *  - nothing is written outside entries [0, natt) of the three outputs, and nothing at all
+ *    when natt is 0 or the call returns PZ_EINVAL;
+ *  - with narr == 0 the four table pointers may be NULL (every row that gets that far is
+ *    PZ_EINDEX).
+ * The slot window keeps Go's int: int(block_slot) - CycleLength wraps for block_slot in
+ * [2^63, 2^63 + 63], where every slot not above block_slot is PZ_ATT_SLOT_LOW. */
 typedef struct pz_att_check_batch {
   uint64_t natt;
   const uint64_t* slot;            /* AttestationRecord.Slot */

@@ -56,7 +56,7 @@ void oracle_att_check(void* h, uint64_t ljs, uint64_t lsr, uint64_t n_recent, ui
     int32_t st = 0;
     if ((int64_t)a->slot > (int64_t)a->block_slot) {
       st = 2;
-    } else if ((int64_t)a->slot < (int64_t)a->block_slot - 64) {
+    } else if ((int64_t)a->slot < (int64_t)(a->block_slot - 64)) { /* Go's int wraps: subtracted unsigned */
       st = 3;
     } else if (a->justified_slot != ljs) {
       st = 4;

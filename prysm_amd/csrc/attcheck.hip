@@ -33,7 +33,7 @@ __device__ __forceinline__ void check_one(const pz_att_check_batch& b, uint64_t 
   uint64_t pstart = 0;
   if ((int64_t)s > (int64_t)bs) {
     st = PZ_ATT_SLOT_HIGH;
-  } else if ((int64_t)s < (int64_t)bs - PZ_CYCLE_LENGTH) {
+  } else if ((int64_t)s < (int64_t)(bs - PZ_CYCLE_LENGTH)) {  // (Go's int wraps: subtracted unsigned)
     st = PZ_ATT_SLOT_LOW;
   } else if (js != b.last_justified_slot) {
     st = PZ_ATT_JUSTIFIED;
@@ -133,7 +133,7 @@ __device__ __forceinline__ void check_one_lds(const pz_att_check_batch& b, const
   uint64_t pstart = 0;
   if ((int64_t)s > (int64_t)bs) {
     st = PZ_ATT_SLOT_HIGH;
-  } else if ((int64_t)s < (int64_t)bs - PZ_CYCLE_LENGTH) {
+  } else if ((int64_t)s < (int64_t)(bs - PZ_CYCLE_LENGTH)) {  // (Go's int wraps: subtracted unsigned)
     st = PZ_ATT_SLOT_LOW;
   } else if (js != b.last_justified_slot) {
     st = PZ_ATT_JUSTIFIED;
@@ -206,7 +206,7 @@ extern "C" __global__ void __launch_bounds__(kPThreads) pz_att_check_p_kernel(pz
   uint32_t* tsh = tab + (ok ? narr + 1 : 0);
   uint32_t* tcm = tsh + (ok ? ne : 0);
   uint32_t* tkk = tcm + (ok ? ne : 0);
-  if (ok) {
+  if (ok && narr) {  // (no array: no table to read, arr_offs may be NULL; every index is out of range)
     for (uint64_t a = tid; a <= narr; a += kPThreads) {
       const uint64_t o = b.arr_offs[a];
       ok = ok && o <= ne && (a == 0 || b.arr_offs[a - 1] <= o);
