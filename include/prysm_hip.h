@@ -1286,10 +1286,13 @@ int pz_dev_block_set_insert_walked(pz_block_set* set, const uint8_t* d_block_has
  * shard32), as pz_attestation_cols for pz_dev_wire_attestations(field_num = 1) (the stored
  * ActiveState's field 1, types/state.go:141), and as the crosslink winners' ShardBlockHash.
  *
- * caps[7], fixed at creation, in the order of the decoder's totals with "rows" first: rows,
- * justified_block_hash bytes, shard_block_hash bytes, bitfield bytes, elements, element bytes,
- * sig values.  Seven running counts live on the device.  Two buffer sets ping-pong for the prune;
- * every bytes column has the 4 readable bytes of slack the digest kernels' contract asks for.
+ * caps[7], in the order of the decoder's totals with "rows" first: rows, justified_block_hash
+ * bytes, shard_block_hash bytes, bitfield bytes, elements, element bytes, sig values.  They are
+ * what the pool starts with: pz_[dev_]att_pool_reserve raises them on the device, as append grows
+ * the Go slice (core.go:223-237), and pz_[dev_]att_pool_need tells what an append would add.
+ * Seven running counts live on the device.  Two buffer sets ping-pong for the prune and the
+ * reserve; every bytes column has the 4 readable bytes of slack the digest kernels' contract asks
+ * for.
  *
  * Append and prune are the same four dependent launches on the caller's stream (size, scan,
  * commit, write: DESIGN.md §3); no workgroup waits for another.  A call that would exceed any of
@@ -1326,7 +1329,7 @@ int pz_dev_att_pool_prune(pz_att_pool* pool, uint64_t last_state_recalc, void* s
  * call was dropped for capacity); the counts are filled all the same. */
 int pz_att_pool_counts(pz_att_pool* pool, uint64_t counts[7]);
 /* PendingAttestations() (types/state.go:164) as device pointers into the live buffer set,
- * valid until the next prune or free; any of the three outputs may be NULL.  No device call. */
+ * valid until the next prune, reserve or free; any of the three outputs may be NULL.  No device call. */
 int pz_att_pool_view(pz_att_pool* pool, pz_attestation_cols* cols, const uint32_t** committee, const uint32_t** shard32);
 /* Host download of PendingAttestations() (types/state.go:164; tests, persistence): the fourteen columns of out (its
  * n_oblique, last_byte and status are not touched; a NULL column is skipped) and committee
@@ -1340,6 +1343,45 @@ int pz_att_pool_read(pz_att_pool* pool, const pz_attestation_cols_out* out, uint
  * bytes exceed cap. */
 int pz_att_pool_shard_block_hashes(pz_att_pool* pool, const uint32_t* rows, uint64_t nrows, uint8_t* out, uint64_t cap,
                                    uint64_t* offs);
+/* The seven capacities now (no reference counterpart: a Go slice's cap is not observable here).
+ * Host only, no device call. */
+int pz_att_pool_capacity(pz_att_pool* pool, uint64_t caps[7]);
+/* append's own growth of PendingAttestations (core.go:223-237; types/state.go:169): the capacities
+ * become max(cap, min_caps) column by column, exactly.  Where every min_caps[c] <= cap[c] nothing
+ * happens and nothing is launched.  Otherwise ONE launch on the caller's stream
+ * (pz_att_pool_move_kernel) copies the live prefix of every column into the other buffer set,
+ * grown first, and the sets swap; the host decides from the capacities it keeps and reads nothing
+ * back.  The seven counts, the rows and their order, every column's contents, committee, shard32
+ * and the sticky error word (both bits) are unchanged, and every entry point of the handle works
+ * on the grown pool.  The set left behind stays allocated, so a kernel already queued over
+ * pz_att_pool_view still reads valid memory, and grows when a prune or a reserve next writes into
+ * it; the pool's own prune scratch follows caps[0].  pz_att_pool_view's pointers are valid until
+ * the next prune, free or reserve.  PZ_EINVAL, before any launch: a NULL pool or min_caps, a
+ * min_caps[c] of 2^40 or more (what pz_att_pool_new refuses).  PZ_EDEVICE: an allocation failed;
+ * the pool is as it was.  Caller's stream, asynchronous, ordered there like every call on the
+ * handle. */
+int pz_dev_att_pool_reserve(pz_att_pool* pool, const uint64_t min_caps[7], void* stream);
+/* The same growth (core.go:223-237; types/state.go:169), synchronous; waits for the stream of the
+ * pool's last call first. */
+int pz_att_pool_reserve(pz_att_pool* pool, const uint64_t min_caps[7]);
+/* The scratch pz_dev_att_pool_need over n rows needs (no reference counterpart). */
+uint64_t pz_att_pool_need_scratch_bytes(uint64_t n);
+/* What pz_[dev_]att_pool_append of these rows would add to the seven counts (the rows
+ * processedAttestations keeps, service.go:299-300), per take column: d_need[k][c] is the sum over
+ * the rows with status[i] == PZ_ATT_PROCESSED and take_k[i] != 0 (a NULL take: every PROCESSED
+ * row; with both NULL the two rows of the output are equal) of the row's seven sizes, an inverted
+ * row counting as the empty row it lands as.  The append's own size and scan launches without a
+ * commit; no pool is touched and no sticky bit is set.  pz_attestation_cols' NULL rules hold.
+ * n == 0 launches nothing and queues a memset: the output is zeros.  PZ_EINVAL, before any launch:
+ * with n > 0 a NULL a or status, offsets without their data column; d_need NULL or not 8-byte
+ * aligned, d_scratch NULL or not 16-byte aligned.  Device pointers, caller's stream, asynchronous. */
+int pz_dev_att_pool_need(const pz_attestation_cols* a, uint64_t n, const int32_t* status,
+                         const uint8_t* take0 /* optional */, const uint8_t* take1 /* optional */,
+                         uint64_t* d_need /* [2][7] */, void* d_scratch, void* stream);
+/* The same sums (service.go:299-300) over host pointers (ranges start at 0), synchronous, on the
+ * current device. */
+int pz_att_pool_need(const pz_attestation_cols* a, uint64_t n, const int32_t* status,
+                     const uint8_t* take0 /* optional */, const uint8_t* take1 /* optional */, uint64_t need[2][7]);
 
 /* ---- R: stateRecalc over the resident pool and vote cache -----------------------------------------
  * The cycle transition (stateRecalc, blockchain/core.go:398-497) as one call: the justification

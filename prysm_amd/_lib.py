@@ -161,6 +161,12 @@ SIGNATURES = {
     "pz_att_pool_view": [vp, vp, vp, vp],
     "pz_att_pool_read": [vp, vp, vp, vp],
     "pz_att_pool_shard_block_hashes": [vp, vp, u64, vp, u64, vp],
+    "pz_att_pool_capacity": [vp, vp],
+    "pz_dev_att_pool_reserve": [vp, vp, vp],
+    "pz_att_pool_reserve": [vp, vp],
+    "pz_att_pool_need_scratch_bytes": [u64],
+    "pz_dev_att_pool_need": [vp, u64, vp, vp, vp, vp, vp, vp],
+    "pz_att_pool_need": [vp, u64, vp, vp, vp, vp],
     "pz_recalc_state_new": [u32, u32, vp, vp, vp, vp, vp, ctypes.c_int, vp],
     "pz_recalc_state_free": [vp],
     "pz_recalc_state_read": [vp, vp, vp, vp, vp, vp, vp],
@@ -409,7 +415,7 @@ _RESTYPES = {"pz_last_error": ctypes.c_char_p, "pz_chain_free": None, "pz_set_se
              "pz_wire_attestations_bound": u64, "pz_wire_attestations_scratch_bytes": u64,
              "pz_unwire_attestations_scratch_bytes": u64, "pz_unwire_blocks_scratch_bytes": u64,
              "pz_vote_cache_free": None, "pz_vote_cache_scratch_bytes": u64, "pz_vote_cache_retain_scratch_bytes": u64,
-             "pz_att_pool_free": None, "pz_att_pool_scratch_bytes": u64,
+             "pz_att_pool_free": None, "pz_att_pool_scratch_bytes": u64, "pz_att_pool_need_scratch_bytes": u64,
              "pz_recent_hashes_free": None, "pz_block_walk_scratch_bytes": u64,
              "pz_block_cycle_scratch_bytes": u64,
              "pz_block_set_free": None, "pz_block_parents_scratch_bytes": u64,

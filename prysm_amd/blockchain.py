@@ -855,20 +855,22 @@ def resident_state_roots(pool, state, recent_hashes, field12, recent_len=None, c
 _NO_T = (1 << 64) - 1  # pz_block_cycle_batch.result's t_index without a transition block
 
 
-class _CachePolicyKeyword(type):
-    """``ResidentChain(..., cache_policy=...)``: the class's call takes the keyword and hands it to
-    ``_set_cache_policy`` behind ``__init__``, whose parameter list is pinned as it stands
-    (tests/test_blockcycle_abi.py)."""
+class _PolicyKeywords(type):
+    """``ResidentChain(..., cache_policy=..., pool_policy=...)``: the class's call takes the keywords
+    and hands them to ``_set_cache_policy`` / ``_set_pool_policy`` behind ``__init__``, whose
+    parameter list is pinned as it stands (tests/test_blockcycle_abi.py)."""
 
-    def __call__(cls, *args, cache_policy="fixed", **kwargs):
-        if cache_policy not in cls.CACHE_POLICIES:  # before any object is made
-            raise PzError(_lib.PZ_EINVAL, "cache_policy %r: one of %s" % (cache_policy, ", ".join(cls.CACHE_POLICIES)))
+    def __call__(cls, *args, cache_policy="fixed", pool_policy="fixed", **kwargs):
+        for what, value, known in (("cache_policy", cache_policy, cls.CACHE_POLICIES), ("pool_policy", pool_policy, cls.POOL_POLICIES)):
+            if value not in known:  # before any object is made
+                raise PzError(_lib.PZ_EINVAL, "%s %r: one of %s" % (what, value, ", ".join(known)))
         self = super().__call__(*args, **kwargs)
         self._set_cache_policy(cache_policy)
+        self._set_pool_policy(pool_policy)
         return self
 
 
-class ResidentChain(metaclass=_CachePolicyKeyword):
+class ResidentChain(metaclass=_PolicyKeywords):
     """blockProcessing (blockchain/service.go:229-363) over the resident objects, transition blocks
     included: ``cache`` (a ``prysm_amd.votes.DeviceVoteCache``), ``pool`` (a
     ``prysm_amd.pending.DevicePendingAttestations``), ``ring`` (a ``DeviceRecentHashes``), ``saved`` (a
@@ -896,9 +898,23 @@ class ResidentChain(metaclass=_CachePolicyKeyword):
     first retains the run's hash log, which already lies on the device (``DeviceVoteCache.retain``):
     every window this call's stateRecalc and any later one can read (votecache_dev.h holds the
     argument and what it leaves out), and reserves only if the log and the need still do not fit.
-    ``cache_retains`` and ``cache_grows`` count them."""
+    ``cache_retains`` and ``cache_grows`` count them.
+
+    ``pool_policy``: the reference's PendingAttestations is a slice that append grows
+    (core.go:223-237), and an append that would exceed one of the pool's seven capacities lands
+    nothing and sets the sticky PZ_ERANGE.  ``"fixed"`` (the default) leaves it at that and queues
+    nothing.  With ``"grow"`` an append never meets that error: the driver keeps upper bounds of the
+    seven counts (one ``pool.counts()`` when the object is made), and per submission
+    ``pz_dev_att_pool_need`` forms on the device what each landing's append would add; its 112 bytes
+    come along in the run's one read, beside the cache policy's.  Where bound + need exceeds a
+    capacity the bounds are first replaced by ``pool.counts()`` (they go stale upward behind a
+    stateRecalc's prune; one wait, on this path only), and if they still do not fit each short
+    column is reserved to ``max(bound + need, 2 * capacity)`` (``DevicePendingAttestations.reserve``
+    on the stream).  ``pool_grows`` counts the reserves that raised a capacity.  Nothing bounds the
+    pool's memory here: the reference's own prune does."""
 
     CACHE_POLICIES = ("fixed", "grow", "retire")
+    POOL_POLICIES = ("fixed", "grow")
 
     def __init__(self, cache, pool, ring, saved, state, shard_and_committees, device=0):
         import torch
@@ -929,12 +945,31 @@ class ResidentChain(metaclass=_CachePolicyKeyword):
         self._slots_ub = 0 if cache_policy == "fixed" else len(self.cache.read(strict=False)[1])
         self._ring_counted = False
 
+    def _set_pool_policy(self, pool_policy):
+        self.pool_policy = pool_policy
+        self.pool_grows = 0  # reserves that raised a capacity ("grow")
+        # host-side upper bounds of the pool's seven counts ("grow"; exact here, stale upward behind a prune)
+        self._pool_ub = None if pool_policy == "fixed" else [int(x) for x in self.pool.counts(strict=False)]
+
+    def _pool_room(self, need):
+        """Before a landing's append under ``"grow"``: the bounds plus ``need`` (seven ints) fit the
+        capacities, or a reserve makes them."""
+        pool = self.pool
+        cap = [int(x) for x in pool.caps]
+        if any(u + a > c for u, a, c in zip(self._pool_ub, need, cap)):
+            self._pool_ub = [int(x) for x in pool.counts(strict=False)]  # the one wait of this path
+            want = [u + a for u, a in zip(self._pool_ub, need)]
+            if any(w > c for w, c in zip(want, cap)):
+                pool.reserve([min(max(w, 2 * c), (1 << 40) - 1) if w > c else c for w, c in zip(want, cap)], device_form=True)
+                self.pool_grows += 1
+        self._pool_ub = [u + a for u, a in zip(self._pool_ub, need)]
+
     RUN_BLOCKS = 1024  # process_all's submission: the scan's tile, and far more than a cycle's blocks of one chain
     CAPS = (256, 256 * 32, 256 * 32, 256 * 8, 256, 256 * 32, 512)  # from_state's pool: rows and bytes of four cycles' blocks
 
     @classmethod
     def from_state(cls, crystallized_bytes, saved_hashes=(), device=0, slot_cap=512, caps=CAPS, hash_stride=32,
-                   cache_policy="fixed"):
+                   cache_policy="fixed", pool_policy="fixed"):
         """NewBeaconChain over a database that holds a CrystallizedState (blockchain/core.go:86-95):
         the state decoded on the device from its stored bytes (``ResidentRecalcState.from_state``;
         exactly the canonical encoding is accepted), a fresh vote cache of ``slot_cap`` slots over
@@ -942,14 +977,15 @@ class ResidentChain(metaclass=_CachePolicyKeyword):
         ring of 128 empty entries -- the reference reloads no ActiveState (core.go:59-64) -- and the
         saved-block set over ``saved_hashes``, the block hashes the database holds.  The committee
         table is taken from the decoded device tensors: no validator and no member visits the host.
-        ``cache_policy``: what a landing does when the cache's slots may not hold it (the class's text)."""
+        ``cache_policy``: what a landing does when the cache's slots may not hold it, and
+        ``pool_policy``: when the pool's capacities may not (the class's text)."""
         from prysm_amd.pending import DevicePendingAttestations, DeviceRecentHashes, DeviceSavedBlocks, ResidentRecalcState
         from prysm_amd.votes import DeviceVoteCache
 
         state = ResidentRecalcState.from_state(crystallized_bytes, device=device, hash_stride=hash_stride)
         return cls(DeviceVoteCache(state.nval, slot_cap, device), DevicePendingAttestations(list(caps), device),
                    DeviceRecentHashes(device=device), DeviceSavedBlocks(list(saved_hashes), device=device), state, None, device,
-                   cache_policy=cache_policy)
+                   cache_policy=cache_policy, pool_policy=pool_policy)
 
     def chain_scalars(self):
         """``(last_justified_slot, last_state_recalc)`` of the chain's CrystallizedState: what a
@@ -1042,7 +1078,10 @@ class ResidentChain(metaclass=_CachePolicyKeyword):
         d = _decode_check(d_bytes, d_offs, n, ljs, lsr, 128, self._narr, self._table, dev, want_committee=True)
         natt, blk, status = d["natt"], d["blk"], d["status"]
         managed = self.cache_policy != "fixed"
-        q = _queue_run(d, nbytes, _fold_eligible(blk["status"], el), saved, 8, extra=16 if managed else 0)
+        grows = self.pool_policy == "grow"
+        # the policies' extras side by side: the cache's two sums (16 bytes), then the pool's need (2 x 7 x 8)
+        x_pool = 16 if managed else 0
+        q = _queue_run(d, nbytes, _fold_eligible(blk["status"], el), saved, 8, extra=x_pool + (112 if grows else 0))
         p = _lib.dptr
         base = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
         log = torch.empty(int(lib.dll.pz_block_cycle_scratch_bytes(n, natt)), dtype=torch.uint8, device=dev)
@@ -1061,12 +1100,16 @@ class ResidentChain(metaclass=_CachePolicyKeyword):
         if managed and natt:  # the oblique elements of the rows each landing tallies: they come along in the read
             nobl = d["att"]["n_oblique"][:natt]
             lands = torch.stack([(nobl * (vote[k, :natt] == ATT_PROCESSED)).sum() for k in (0, 1)])
-            q["word"][q["at"]["extra"]:].copy_(lands.view(torch.uint8))
+            q["word"][q["at"]["extra"]:q["at"]["extra"] + 16].copy_(lands.view(torch.uint8))
+        if grows and natt:  # what each landing's append would add to the pool's counts: likewise
+            need = pool.need_columns(d["att"], natt, status.contiguous(), take[0], take[1])
+            q["word"][q["at"]["extra"] + x_pool:].copy_(need.view(torch.uint8).reshape(-1))
         empty = (0, 0, int(bool(self.has_candidate)), int(self.candidate_slot) if self.has_candidate else 0, _NO_T, 0, 0, lag)
         (_, _, has, cslot, t_index, t_rank, t_slot, lag_out), panic, out = _read_run(q, d, saved, empty)
         out["t_index"], out["lag"] = None if t_index == _NO_T else t_index, lag_out
         nlog = 129 + out["ncand"]  # the log entries the tallies read
-        obl = [int(x) for x in np.frombuffer(q["extra_host"].tobytes(), dtype=np.uint64)] if managed else None
+        obl = [int(x) for x in np.frombuffer(q["extra_host"][:16].tobytes(), dtype=np.uint64)] if managed else None
+        pneed = np.frombuffer(q["extra_host"][x_pool:].tobytes(), dtype=np.uint64).reshape(2, 7) if grows else None
         counted = [False]  # the run's log is counted in _slots_ub
 
         def room(phase):  # before a landing's tally: the bounds fit, or the policy makes them
@@ -1087,6 +1130,8 @@ class ResidentChain(metaclass=_CachePolicyKeyword):
                 room(phase)
             cache.tally_columns(d["att"], natt, vote[phase], d["committee"], d["parents_start"], log, self._members,
                                 self._table[3], state.balance)
+            if grows:
+                self._pool_room([int(x) for x in pneed[phase]])
             pool.append_columns(d["att"], natt, status.contiguous(), d["committee"], take=take[phase])
 
         if not panic:

@@ -25,6 +25,15 @@
 //             writes nothing.
 // A prune selects from the live buffer set into the other one at base 0, then the sets swap.
 //
+// The capacities grow as the Go slice does under append (core.go:223-237; types/state.go:169):
+// pz_[dev_]att_pool_reserve grows the other buffer set to max(cap, min_caps) and ONE launch,
+// pz_att_pool_move_kernel, copies the live prefix of every column there -- the seven counts are read
+// on the device, the host knows only the capacities -- then the sets swap.  The set left behind
+// keeps its buffers, so a kernel queued over a view still reads valid memory; it grows when a prune
+// or a reserve next writes into it (DevBuf::reserve, a no-op while it is large enough).
+// pz_[dev_]att_pool_need is the size and scan launches of an append without its commit: the seven
+// sums a landing would add, for up to two take columns.
+//
 // Reads: only the rows' ranges of the source columns.  Writes: only inside the ranges the scan
 // assigns, which the commit has checked against the capacities.
 #include <hip/hip_runtime.h>
@@ -43,7 +52,7 @@
 namespace pz {
 namespace {
 
-constexpr int kSetBufs = kAttNCols + 2;  // pz_attestation_cols' columns (att_cols.h's order), committee, shard32
+constexpr int kSetBufs = kApSetBufs;  // pz_attestation_cols' columns (att_cols.h's order), committee, shard32
 
 }  // namespace
 }  // namespace pz
@@ -110,14 +119,48 @@ __device__ __forceinline__ bool ap_keep(const ApArgs& a, uint64_t i) {
 extern "C" __global__ void __launch_bounds__(kTile) pz_att_pool_size_kernel(ApArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
   const uint64_t n = a.prune ? a.counts[kApRows] : a.n;
-  uint64_t sz[kApCols] = {0, 0, 0, 0, 0, 0, 0};
-  if (i < n && ap_keep(a, i)) {
-    const ApRow r = ap_row(a.src, i);
-    if (r.inverted) atomicOr((unsigned long long*)(a.counts + kApCols), (unsigned long long)kApErrInverted);
-#pragma unroll
-    for (int c = 0; c < kApCols; ++c) sz[c] = r.sz[c];
-  }
+  uint64_t sz[kApCols];
+  if (ap_kept_sizes(i < n && ap_keep(a, i), a.src, i, sz))
+    atomicOr((unsigned long long*)(a.counts + kApCols), (unsigned long long)kApErrInverted);
   tile_sums<kApCols>(sz, a.tiles, a.ntiles);
+}
+
+// ---- need: the size phase of an append for two take columns, no pool --------------------------
+struct ApNeedArgs {
+  pz_attestation_cols src;
+  const int32_t* status;
+  const uint8_t* take[2];
+  uint64_t n, ntiles;
+  uint64_t* tiles;  // [2][7][ntiles]: fourteen columns for the scan
+};
+
+extern "C" __global__ void __launch_bounds__(kTile) pz_att_pool_need_kernel(ApNeedArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+  const uint32_t k = blockIdx.y;
+  uint64_t sz[kApCols];
+  (void)ap_kept_sizes(i < a.n && ap_keep_append(a.status, a.take[k], i), a.src, i, sz);
+  tile_sums<kApCols>(sz, a.tiles + (uint64_t)k * kApCols * a.ntiles, a.ntiles);
+}
+
+// ---- move: every column's live prefix into the grown buffer set -----------------------------------
+struct ApMoveArgs {
+  const uint8_t* src[kSetBufs];
+  uint8_t* dst[kSetBufs];
+  ApColRule rule[kSetBufs];
+  uint64_t cap[kApCols];   // the capacities the source set was filled under: a count never exceeds its own
+  const uint64_t* counts;  // [7], on the device
+};
+
+// A row of workgroups per buffer (blockIdx.y), a grid-wide lane index along it: the sixteen columns'
+// round trips overlap instead of queueing behind each other.  Plain loads and stores, no workgroup
+// waits for another.  The governing count is clamped to the old capacity, so no access leaves
+// either buffer set whatever the words hold.
+extern "C" __global__ void __launch_bounds__(kTile) pz_att_pool_move_kernel(ApMoveArgs a) {
+  const uint64_t t = (uint64_t)blockIdx.x * kTile + threadIdx.x, T = (uint64_t)gridDim.x * kTile;
+  const uint32_t k = blockIdx.y;
+  const ApColRule r = a.rule[k];
+  const uint64_t n = a.counts[r.count], cap = a.cap[r.count];
+  ap_move_lane(a.dst[k], a.src[k], ap_col_live_bytes(r, n < cap ? n : cap), t, T);
 }
 
 // ---- 3: commit (one lane) --------------------------------------------------------------------
@@ -346,6 +389,88 @@ int report(int sticky) {
   return PZ_OK;
 }
 
+// ---- reserve and need, host side ---------------------------------------------------------------
+// Set s's buffers hold at least `cap` (grow-only, buffer by buffer: nothing happens where they do).
+int grow_set(pz_att_pool* h, int s, const uint64_t cap[kApCols]) {
+  int rc = PZ_OK;
+  for (int k = 0; k < kSetBufs && !rc; ++k) rc = h->set[s][k].reserve((size_t)buf_bytes(cap, k));
+  return rc;
+}
+
+int check_reserve(const pz_att_pool* h, const uint64_t* min_caps) {
+  if (!h) return fail(PZ_EINVAL, "attestation pool is null");
+  if (!min_caps) return fail(PZ_EINVAL, "min_caps is null");
+  for (int c = 0; c < kApCols; ++c)
+    if (min_caps[c] >> 40) return fail(PZ_EINVAL, "capacity %d is %llu: 2^40 or more", c, (unsigned long long)min_caps[c]);
+  return PZ_OK;
+}
+
+// The live prefixes into the other set, grown to new_cap, on s; then the sets swap.  An allocation
+// failure leaves the pool as it was (the other set holds no rows).  ev (the A/B library's timed
+// entry): one event pair around the launch.
+int enqueue_reserve(pz_att_pool* h, const uint64_t new_cap[kApCols], hipStream_t s, Events* ev = nullptr) {
+  const int other = h->live ^ 1;
+  int rc;
+  if ((rc = grow_set(h, other, new_cap)) || (rc = h->scratch.reserve(scratch_bytes(new_cap[kApRows])))) return rc;
+  ApMoveArgs a;
+  std::memset(&a, 0, sizeof a);
+  uint64_t most = 0;  // the largest column's bytes at the old capacities: the grid
+  for (int k = 0; k < kSetBufs; ++k) {
+    a.src[k] = static_cast<const uint8_t*>(h->set[h->live][k].ptr);
+    a.dst[k] = static_cast<uint8_t*>(h->set[other][k].ptr);
+    a.rule[k] = ap_col_rule(k);
+    most = std::max(most, ap_col_live_bytes(a.rule[k], h->cap));
+  }
+  std::memcpy(a.cap, h->cap, sizeof a.cap);
+  a.counts = static_cast<const uint64_t*>(h->words.ptr);
+  const uint64_t blocks = std::min<uint64_t>(std::max<uint64_t>((most + kTile * 64 - 1) / (kTile * 64), 1), 1024);
+  h->last = s;
+  stamp(ev, 0, s);
+  hipLaunchKernelGGL(pz_att_pool_move_kernel, dim3((uint32_t)blocks, kSetBufs), dim3(kTile), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "pz_att_pool_move_kernel");
+  stamp(ev, 1, s);
+  h->live = other;
+  std::memcpy(h->cap, new_cap, sizeof h->cap);
+  return PZ_OK;
+}
+
+uint64_t need_scratch_bytes(uint64_t n) { return pad256(2 * kApCols * tiles_of(n) * 8 + 16); }
+
+// What can be told about a need call without reading a column; 1: nothing to count.
+int check_need(const pz_attestation_cols* a, uint64_t n, const int32_t* status) {
+  if (n == 0) return 1;
+  if (!a) return fail(PZ_EINVAL, "columns are null");
+  if (!status) return fail(PZ_EINVAL, "need: null status");
+  if ((a->justified_block_hash_offs && !a->justified_block_hash) || (a->shard_block_hash_offs && !a->shard_block_hash) ||
+      (a->attester_bitfield_offs && !a->attester_bitfield) ||
+      (a->oblique_first && (!a->oblique_offs || !a->oblique_parent_hashes)) || (a->aggregate_sig_first && !a->aggregate_sig))
+    return fail(PZ_EINVAL, "offsets without their data column");
+  if (n >> 38) return fail(PZ_EINVAL, "more than 2^38 rows");
+  return PZ_OK;
+}
+
+// The two launches on s (n > 0); d_need: [2][7].  ev: three events, one before the first launch and
+// one after each.
+int enqueue_need(const pz_attestation_cols& cols, uint64_t n, const int32_t* status, const uint8_t* take0,
+                 const uint8_t* take1, uint64_t* d_need, void* d_scratch, hipStream_t s, Events* ev = nullptr) {
+  ApNeedArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.src = cols;
+  a.status = status;
+  a.take[0] = take0, a.take[1] = take1;
+  a.n = n, a.ntiles = tiles_of(n);
+  a.tiles = static_cast<uint64_t*>(d_scratch);
+  hipError_t e;
+  stamp(ev, 0, s);
+  hipLaunchKernelGGL(pz_att_pool_need_kernel, dim3((uint32_t)a.ntiles, 2), dim3(kTile), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "pz_att_pool_need_kernel");
+  stamp(ev, 1, s);
+  if ((e = launch_tile_scan(a.tiles, a.ntiles, 2u * kApCols, d_need, s)) != hipSuccess) return hip_fail(e, "pz_unwire_scan_kernel");
+  stamp(ev, 2, s);
+  return PZ_OK;
+}
+
 }  // namespace
 
 int att_pool_peek(pz_att_pool* h, ApView* v, hipStream_t s) {
@@ -443,6 +568,7 @@ int pz_dev_att_pool_prune(pz_att_pool* h, uint64_t last_state_recalc, void* stre
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   if (h->rows_ub == 0) return PZ_OK;  // nothing was ever appended since the last exact count of 0
+  if ((rc = grow_set(h, h->live ^ 1, h->cap))) return rc;  // (the set a reserve left behind: it grows here)
   if ((rc = enqueue(h, prune_args(h, last_state_recalc), h->scratch.ptr, static_cast<hipStream_t>(stream)))) return rc;
   h->live ^= 1;
   return PZ_OK;
@@ -517,7 +643,105 @@ int pz_att_pool_shard_block_hashes(pz_att_pool* h, const uint32_t* rows, uint64_
   return PZ_OK;
 }
 
+int pz_att_pool_capacity(pz_att_pool* h, uint64_t caps[7]) {
+  if (!h || !caps) return fail(PZ_EINVAL, "attestation pool / caps is null");
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::memcpy(caps, h->cap, sizeof h->cap);
+  return PZ_OK;
+}
+
+int pz_dev_att_pool_reserve(pz_att_pool* h, const uint64_t min_caps[7], void* stream) {
+  int rc = check_reserve(h, min_caps);
+  if (rc) return rc;
+  if ((rc = h->use())) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  uint64_t new_cap[kApCols];
+  if (!ap_reserve_caps(h->cap, min_caps, new_cap)) return PZ_OK;
+  return enqueue_reserve(h, new_cap, static_cast<hipStream_t>(stream));
+}
+
+int pz_att_pool_reserve(pz_att_pool* h, const uint64_t min_caps[7]) {
+  int rc = check_reserve(h, min_caps);
+  if (rc) return rc;
+  HostForm f(h, "attestation pool reserve");
+  if (f.rc) return f.rc;
+  uint64_t new_cap[kApCols];
+  if (!ap_reserve_caps(h->cap, min_caps, new_cap)) return PZ_OK;
+  if ((rc = enqueue_reserve(h, new_cap, f.st.s))) return rc;
+  return f.st.sync();
+}
+
+uint64_t pz_att_pool_need_scratch_bytes(uint64_t n) { return need_scratch_bytes(n); }
+
+int pz_dev_att_pool_need(const pz_attestation_cols* a, uint64_t n, const int32_t* status, const uint8_t* take0,
+                         const uint8_t* take1, uint64_t* d_need, void* d_scratch, void* stream) {
+  int rc = check_need(a, n, status);
+  if (rc < 0) return rc;
+  if (!d_need || (reinterpret_cast<uintptr_t>(d_need) & 7)) return fail(PZ_EINVAL, "d_need must be an 8-B aligned device pointer");
+  if (!d_scratch || !aligned16(d_scratch)) return fail(PZ_EINVAL, "d_scratch must be a 16-B aligned device pointer");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (rc == 1) {  // no row: zeros, in stream order
+    hipError_t e = hipMemsetAsync(d_need, 0, 2 * kApCols * 8, s);
+    return e == hipSuccess ? PZ_OK : hip_fail(e, "hipMemsetAsync");
+  }
+  return enqueue_need(*a, n, status, take0, take1, d_need, d_scratch, s);
+}
+
+int pz_att_pool_need(const pz_attestation_cols* ha, uint64_t n, const int32_t* status, const uint8_t* take0,
+                     const uint8_t* take1, uint64_t need[2][7]) {
+  int rc = check_need(ha, n, status);
+  if (rc < 0) return rc;
+  if (!need) return fail(PZ_EINVAL, "need is null");
+  std::memset(need, 0, 2 * kApCols * 8);
+  if (rc == 1) return PZ_OK;
+  HostForm f(nullptr, "attestation pool need");
+  if (f.rc) return f.rc;
+  Stager& st = f.st;
+  pz_attestation_cols d;
+  stage_att_cols(st, *ha, n, kAttAllCols, &d);
+  const int32_t* d_status = st.up(status, n);
+  const uint8_t* d_take0 = take0 ? st.up(take0, n) : nullptr;
+  const uint8_t* d_take1 = take1 ? st.up(take1, n) : nullptr;
+  uint64_t* d_need = st.up<uint64_t>(nullptr, 2 * kApCols);
+  uint8_t* scr = st.up<uint8_t>(nullptr, need_scratch_bytes(n));
+  if (st.rc) return st.rc;
+  if ((rc = enqueue_need(d, n, d_status, d_take0, d_take1, d_need, scr, st.s))) return rc;
+  st.down(&need[0][0], d_need, 2 * kApCols);
+  return st.sync();
+}
+
 #ifdef PZ_AB_BUILD
+// (tools/attpool_reserve_probe.py) pz_dev_att_pool_reserve with one event pair on its launch;
+// synchronises and returns the launch's milliseconds in ms[0].  PZ_EINVAL where nothing would grow.
+int pz_debug_att_pool_reserve_timed(pz_att_pool* h, const uint64_t min_caps[7], void* stream, float ms[1]) {
+  int rc = check_reserve(h, min_caps);
+  if (rc) return rc;
+  if (!ms) return fail(PZ_EINVAL, "null ms");
+  if ((rc = h->use())) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  uint64_t new_cap[kApCols];
+  if (!ap_reserve_caps(h->cap, min_caps, new_cap)) return fail(PZ_EINVAL, "nothing to time");
+  Events ev;
+  if ((rc = ev.create(2))) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  rc = enqueue_reserve(h, new_cap, s, &ev);
+  return ev.elapsed(rc, ms, nullptr, 1, s, "timed attestation pool reserve");
+}
+
+// (tools/attpool_reserve_probe.py) pz_dev_att_pool_need (n > 0) with one event pair per launch;
+// synchronises and returns the two launches' milliseconds (need, scan) in ms[0..2).
+int pz_debug_att_pool_need_timed(const pz_attestation_cols* a, uint64_t n, const int32_t* status, const uint8_t* take0,
+                                 const uint8_t* take1, uint64_t* d_need, void* d_scratch, void* stream, float ms[2]) {
+  int rc = check_need(a, n, status);
+  if (rc) return rc < 0 ? rc : fail(PZ_EINVAL, "nothing to time");
+  if (!ms || !d_need || !d_scratch) return fail(PZ_EINVAL, "null pointer");
+  Events ev;
+  if ((rc = ev.create(3))) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  rc = enqueue_need(*a, n, status, take0, take1, d_need, d_scratch, s, &ev);
+  return ev.elapsed(rc, ms, nullptr, 2, s, "timed attestation pool need");
+}
+
 // (tools/attpool_probe.py) The long-range threshold of the write launch (0: the product's); returns
 // the previous one.  At least 16: the wave copy's tail is the range's last 16 bytes.
 uint64_t pz_debug_att_pool_long_bytes(uint64_t bytes) {
@@ -545,6 +769,7 @@ int pz_debug_att_pool_timed(pz_att_pool* h, const pz_attestation_cols* a, uint64
     rc = enqueue(h, append_args(h, *a, n, status, committee, take), d_scratch, s, &ev);
     if (!rc) h->rows_ub = std::min(h->cap[kApRows], h->rows_ub + n);
   } else {
+    if ((rc = grow_set(h, h->live ^ 1, h->cap))) return rc;
     rc = enqueue(h, prune_args(h, last_state_recalc), h->scratch.ptr, s, &ev);
     if (!rc) h->live ^= 1;
   }

@@ -174,7 +174,7 @@ struct VcView {
 // Fills *v and records s as the stream the cache's reads wait for.
 int vote_cache_view(pz_vote_cache* h, VcView* v, hipStream_t s);
 
-// The pool's live buffer set and its device counts ([7], rows first), valid until the next prune.
+// The pool's live buffer set and its device counts ([7], rows first), valid until the next prune or reserve.
 struct ApView {
   int device;
   uint64_t rows_cap, rows_ub;

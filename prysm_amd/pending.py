@@ -193,10 +193,12 @@ def recent_of(recent, recent_len=None):
 
 
 class DevicePendingAttestations(_lib.Handle):
-    """``caps``: the seven capacities (``CAPS``' order), fixed for the pool's lifetime.  A call that
-    would exceed one changes nothing (PZ_ERANGE, sticky); a kept row with an inverted range lands
-    empty (PZ_EINVAL, sticky).  Every read raises the sticky error; ``strict=False`` returns what the
-    pool holds regardless."""
+    """``caps``: the seven capacities (``CAPS``' order) the pool starts with; :meth:`reserve` raises
+    them on the device, as append grows the reference's slice (core.go:223-237), and ``self.caps``
+    stays the current ones.  A call that would exceed one changes nothing (PZ_ERANGE, sticky) --
+    :meth:`need_columns` tells beforehand what an append would add; a kept row with an inverted
+    range lands empty (PZ_EINVAL, sticky).  Every read raises the sticky error; ``strict=False``
+    returns what the pool holds regardless."""
     _FREE = "pz_att_pool_free"
     _STICKY = (_lib.PZ_EINVAL, _lib.PZ_ERANGE)
 
@@ -238,6 +240,57 @@ class DevicePendingAttestations(_lib.Handle):
         On the current stream, asynchronous."""
         lib.call("pz_dev_att_pool_prune", self._h, int(last_state_recalc), self._stream())
 
+    def reserve(self, min_caps, device_form=False):
+        """append's own growth of the list (core.go:223-237): the capacities become
+        ``max(caps, min_caps)`` column by column, exactly; where none rises nothing is launched.  One
+        launch moves the live rows, whose counts the host does not read; counts, rows, contents and
+        the sticky error are unchanged (``pz_[dev_]att_pool_reserve``; ``device_form``: on the
+        current stream, asynchronous).  Addresses from :meth:`view` taken before it stay readable by
+        what is already queued but are no longer the pool."""
+        min_caps = np.ascontiguousarray(min_caps, dtype=np.uint64)
+        assert min_caps.shape == (7,)
+        if device_form:
+            lib.call("pz_dev_att_pool_reserve", self._h, min_caps.ctypes.data, self._stream())
+        else:
+            lib.call("pz_att_pool_reserve", self._h, min_caps.ctypes.data)
+        self.caps = self.capacity()
+
+    def capacity(self):
+        """The seven capacities now (``CAPS``' order) as a uint64 array (``pz_att_pool_capacity``;
+        the host's own record, no device call)."""
+        out = np.zeros(7, dtype=np.uint64)
+        lib.call("pz_att_pool_capacity", self._h, out.ctypes.data)
+        return out
+
+    @staticmethod
+    def need_columns(cols, n, status, take0=None, take1=None):
+        """What :meth:`append_columns` of these rows would add to the seven counts, for ``take0`` and
+        for ``take1`` (None: every PROCESSED row): a (2, 7) int64 device tensor, left on the device.
+        The append's size and scan launches without a commit, on the current stream, asynchronous
+        (``pz_dev_att_pool_need``)."""
+        import torch
+
+        c = _lib.att_cols(cols)
+        dev = status.device
+        need = torch.empty((2, 7), dtype=torch.int64, device=dev)
+        scratch = torch.empty(max(int(lib.dll.pz_att_pool_need_scratch_bytes(n)), 16), dtype=torch.uint8, device=dev)
+        p = _lib.dptr
+        lib.call("pz_dev_att_pool_need", _lib.ctypes.byref(c), n, p(status), p(take0), p(take1), need.data_ptr(),
+                 scratch.data_ptr(), _lib.stream_ptr(dev))
+        return need
+
+    @staticmethod
+    def need_host(cols, n, status, take0=None, take1=None):
+        """The same sums over host arrays, a (2, 7) uint64 array (``pz_att_pool_need``, synchronous)."""
+        c = _lib.att_cols(cols)
+        status = np.ascontiguousarray(status, dtype=np.int32)
+        take0 = None if take0 is None else np.ascontiguousarray(take0, dtype=np.uint8)
+        take1 = None if take1 is None else np.ascontiguousarray(take1, dtype=np.uint8)
+        need = np.zeros((2, 7), dtype=np.uint64)
+        lib.call("pz_att_pool_need", _lib.ctypes.byref(c), n, _lib.ptr(status), _lib.ptr(take0), _lib.ptr(take1),
+                 need.ctypes.data)
+        return need
+
     # ---- reads -------------------------------------------------------------------------------
     def counts(self, strict=True):
         """The seven counts (``CAPS``' order) as a uint64 array; waits for the last call."""
@@ -250,7 +303,7 @@ class DevicePendingAttestations(_lib.Handle):
 
     def view(self):
         """``(AttestationCols, committee, shard32)``: device addresses into the live buffer set,
-        valid until the next prune."""
+        valid until the next prune or reserve."""
         c = _lib.AttestationCols()
         comm, s32 = _lib.ctypes.c_void_p(), _lib.ctypes.c_void_p()
         lib.call("pz_att_pool_view", self._h, _lib.ctypes.byref(c), _lib.ctypes.byref(comm), _lib.ctypes.byref(s32))
