@@ -855,22 +855,102 @@ def resident_state_roots(pool, state, recent_hashes, field12, recent_len=None, c
 _NO_T = (1 << 64) - 1  # pz_block_cycle_batch.result's t_index without a transition block
 
 
-class _PolicyKeywords(type):
-    """``ResidentChain(..., cache_policy=..., pool_policy=...)``: the class's call takes the keywords
-    and hands them to ``_set_cache_policy`` / ``_set_pool_policy`` behind ``__init__``, whose
-    parameter list is pinned as it stands (tests/test_blockcycle_abi.py)."""
+class _CacheRoom:
+    """``ResidentChain``'s ``cache_policy`` (its text has the rules) over ``cache``, a
+    ``DeviceVoteCache``: the bounds, the counters and every step that is the policy's own.  Under
+    ``"fixed"`` it asks for no byte of the read, queues nothing and never calls ``cache``."""
 
-    def __call__(cls, *args, cache_policy="fixed", pool_policy="fixed", **kwargs):
-        for what, value, known in (("cache_policy", cache_policy, cls.CACHE_POLICIES), ("pool_policy", pool_policy, cls.POOL_POLICIES)):
-            if value not in known:  # before any object is made
-                raise PzError(_lib.PZ_EINVAL, "%s %r: one of %s" % (what, value, ", ".join(known)))
-        self = super().__call__(*args, **kwargs)
-        self._set_cache_policy(cache_policy)
-        self._set_pool_policy(pool_policy)
-        return self
+    def __init__(self, cache, policy):
+        self.cache, self.policy = cache, policy
+        self.extra_bytes = 0 if policy == "fixed" else 16  # of the run's one read: the two landings' oblique sums
+        self.retains = 0  # retains queued ("retire")
+        self.grows = 0    # reserves that raised the capacity ("grow", "retire")
+        # host-side upper bounds, never read back: the slots in use, and whether the ring's 129 hashes
+        # are counted in it already (the landing of a run counts the run's whole log, which holds the next ring)
+        self.slots_ub = len(cache.read(strict=False)[1]) if self.extra_bytes else 0
+        self.ring_counted = False
+        self._run_counted = False  # the run's log is counted in slots_ub: at most once across its two landings
+
+    def queue(self, dst, n_oblique, vote):
+        """Queues into ``dst``, its bytes of the read-back buffer, the oblique elements of the rows
+        each landing tallies (``vote``: the two landings' vote statuses of the run's rows)."""
+        if self.extra_bytes:
+            import torch
+
+            dst.copy_(torch.stack([(n_oblique * (vote[k] == ATT_PROCESSED)).sum() for k in (0, 1)]).view(torch.uint8))
+
+    def parse(self, got):
+        """The two landings' oblique sums from its bytes of the read."""
+        return [int(x) for x in np.frombuffer(got.tobytes(), dtype=np.uint64)] if self.extra_bytes else [0, 0]
+
+    def begin(self):
+        """Before the first landing of a run that lands."""
+        self._run_counted = False
+
+    def fit(self, oblique, nlog, log):
+        """Before a landing's tally, which adds ``oblique`` slots at most beside the first ``nlog``
+        hashes of ``log``: the bounds fit, or the policy makes them."""
+        if not self.extra_bytes:
+            return
+        cache = self.cache
+        need = oblique + (0 if self._run_counted else nlog - (129 if self.ring_counted else 0))
+        if self.slots_ub + need > cache.slot_cap:
+            if self.policy == "retire":  # the kept entries and the log's new ones are the log's hashes
+                cache.retain(log[:32 * nlog])
+                self.retains += 1
+                self.slots_ub, need = nlog, oblique
+            if self.slots_ub + need > cache.slot_cap:
+                cache.reserve(max(self.slots_ub + need, min(2 * cache.slot_cap, 1 << 30)), device_form=True)
+                self.grows += 1
+        self.slots_ub += need
+        self._run_counted = True
+
+    def end(self, ncand):
+        """Behind a run that landed: the next ring is log entries [ncand, ncand + 129), counted iff
+        this run's log was, or nothing rolled."""
+        self.ring_counted = self._run_counted or (self.ring_counted and ncand == 0)
 
 
-class ResidentChain(metaclass=_PolicyKeywords):
+class _PoolRoom:
+    """``ResidentChain``'s ``pool_policy`` (its text has the rules) over ``pool``, a
+    ``DevicePendingAttestations``, as :class:`_CacheRoom` is the cache's."""
+
+    def __init__(self, pool, policy):
+        self.pool = pool
+        self.extra_bytes = 0 if policy == "fixed" else 112  # of the run's one read: the two landings' seven needs
+        self.grows = 0  # reserves that raised a capacity
+        # host-side upper bounds of the pool's seven counts (exact here, stale upward behind a prune)
+        self.counts_ub = [int(x) for x in pool.counts(strict=False)] if self.extra_bytes else None
+
+    def queue(self, dst, cols, n, status, take):
+        """Queues into ``dst``, its bytes of the read-back buffer, what each landing's append of the
+        run's rows would add to the seven counts (``take``: the two landings' take columns)."""
+        if self.extra_bytes:
+            import torch
+
+            dst.copy_(self.pool.need_columns(cols, n, status, take[0], take[1]).view(torch.uint8).reshape(-1))
+
+    def parse(self, got):
+        """The two landings' seven needs from its bytes of the read."""
+        return np.frombuffer(got.tobytes(), dtype=np.uint64).reshape(2, 7).tolist() if self.extra_bytes else [None, None]
+
+    def fit(self, need):
+        """Before a landing's append, which adds ``need`` (seven ints) to the counts: the bounds fit
+        the capacities, or a reserve makes them."""
+        if not self.extra_bytes:
+            return
+        pool = self.pool
+        cap = [int(x) for x in pool.caps]
+        if any(u + a > c for u, a, c in zip(self.counts_ub, need, cap)):
+            self.counts_ub = [int(x) for x in pool.counts(strict=False)]  # the one wait of this path
+            want = [u + a for u, a in zip(self.counts_ub, need)]
+            if any(w > c for w, c in zip(want, cap)):
+                pool.reserve([min(max(w, 2 * c), (1 << 40) - 1) if w > c else c for w, c in zip(want, cap)], device_form=True)
+                self.grows += 1
+        self.counts_ub = [u + a for u, a in zip(self.counts_ub, need)]
+
+
+class ResidentChain:
     """blockProcessing (blockchain/service.go:229-363) over the resident objects, transition blocks
     included: ``cache`` (a ``prysm_amd.votes.DeviceVoteCache``), ``pool`` (a
     ``prysm_amd.pending.DevicePendingAttestations``), ``ring`` (a ``DeviceRecentHashes``), ``saved`` (a
@@ -886,6 +966,10 @@ class ResidentChain(metaclass=_PolicyKeywords):
     apart: CalculateRewards writes the balances in place (casper/incentives.go:22-28) on the slice
     stateRecalc hands to the new state (core.go:468), so the chain's old CrystallizedState tallies
     with the rewarded balances from the transition block on.
+
+    The two policies are keyword-only arguments, checked before any other argument is touched.
+    Each one's bounds, counters and steps are one object's (``_CacheRoom``, ``_PoolRoom``), which a
+    landing asks for room (``fit``) before its tally and before its append.
 
     ``cache_policy``: the reference's map only grows, and a tally that needs more slots than the
     cache has left lands nothing and sets the sticky PZ_ERANGE.  ``"fixed"`` (the default) leaves it
@@ -916,10 +1000,14 @@ class ResidentChain(metaclass=_PolicyKeywords):
     CACHE_POLICIES = ("fixed", "grow", "retire")
     POOL_POLICIES = ("fixed", "grow")
 
-    def __init__(self, cache, pool, ring, saved, state, shard_and_committees, device=0):
+    def __init__(self, cache, pool, ring, saved, state, shard_and_committees, device=0, *, cache_policy="fixed", pool_policy="fixed"):
+        for what, value, known in (("cache_policy", cache_policy, self.CACHE_POLICIES), ("pool_policy", pool_policy, self.POOL_POLICIES)):
+            if value not in known:  # before any argument is touched
+                raise PzError(_lib.PZ_EINVAL, "%s %r: one of %s" % (what, value, ", ".join(known)))
         import torch
 
         self.cache, self.pool, self.ring, self.saved, self.state = cache, pool, ring, saved, state
+        self.cache_policy, self.pool_policy = cache_policy, pool_policy
         self.device = device
         dev = torch.device("cuda", device)
         if shard_and_committees is None:  # (from_state: the table as the loader left it on the device)
@@ -935,34 +1023,11 @@ class ResidentChain(metaclass=_PolicyKeywords):
         self.calls = 0      # submissions so far: one upload and one read each
         self.resubmits = 0  # of them, runs submitted again without the blocks past their stop
         self.spent = False  # a call failed after its host read: the objects no longer match the carry
+        self._cache_room, self._pool_room = _CacheRoom(cache, cache_policy), _PoolRoom(pool, pool_policy)
 
-    def _set_cache_policy(self, cache_policy):
-        self.cache_policy = cache_policy
-        self.cache_retains = 0  # retains the policy has queued ("retire")
-        self.cache_grows = 0    # reserves that raised the capacity ("grow", "retire")
-        # host-side upper bounds, never read back: the slots in use, and whether the ring's 129 hashes
-        # are counted in it already (the landing of a run counts the run's whole log, which holds the next ring)
-        self._slots_ub = 0 if cache_policy == "fixed" else len(self.cache.read(strict=False)[1])
-        self._ring_counted = False
-
-    def _set_pool_policy(self, pool_policy):
-        self.pool_policy = pool_policy
-        self.pool_grows = 0  # reserves that raised a capacity ("grow")
-        # host-side upper bounds of the pool's seven counts ("grow"; exact here, stale upward behind a prune)
-        self._pool_ub = None if pool_policy == "fixed" else [int(x) for x in self.pool.counts(strict=False)]
-
-    def _pool_room(self, need):
-        """Before a landing's append under ``"grow"``: the bounds plus ``need`` (seven ints) fit the
-        capacities, or a reserve makes them."""
-        pool = self.pool
-        cap = [int(x) for x in pool.caps]
-        if any(u + a > c for u, a, c in zip(self._pool_ub, need, cap)):
-            self._pool_ub = [int(x) for x in pool.counts(strict=False)]  # the one wait of this path
-            want = [u + a for u, a in zip(self._pool_ub, need)]
-            if any(w > c for w, c in zip(want, cap)):
-                pool.reserve([min(max(w, 2 * c), (1 << 40) - 1) if w > c else c for w, c in zip(want, cap)], device_form=True)
-                self.pool_grows += 1
-        self._pool_ub = [u + a for u, a in zip(self._pool_ub, need)]
+    cache_retains = property(lambda self: self._cache_room.retains)
+    cache_grows = property(lambda self: self._cache_room.grows)
+    pool_grows = property(lambda self: self._pool_room.grows)
 
     RUN_BLOCKS = 1024  # process_all's submission: the scan's tile, and far more than a cycle's blocks of one chain
     CAPS = (256, 256 * 32, 256 * 32, 256 * 8, 256, 256 * 32, 512)  # from_state's pool: rows and bytes of four cycles' blocks
@@ -1054,14 +1119,25 @@ class ResidentChain(metaclass=_PolicyKeywords):
 
     def _submit(self, data, offsets, eligible, want_digests):
         """One upload, the device queue, one read, and -- unless the gate's panic bit is set -- the
-        landing.  Returns ``(out, panic)``; with ``panic`` nothing has landed and the carry is as it was."""
+        landing.  Returns ``(out, panic)``; with ``panic`` nothing has landed, and the carry and the
+        policies' bounds are as they were."""
+        up = self._upload(data, offsets, eligible)
+        self.calls += 1
+        run = self._queue(*up)
+        out, panic = self._read(run)
+        if not panic:
+            self._land_run(run)
+        q = run["q"]
+        return _run_outputs(out, run["d"], q["walk"], q["block_status"], q["block_hash"], run["log"], want_digests), panic
+
+    def _upload(self, data, offsets, eligible):
+        """The one upload, ``offsets | eligible | bytes``, the bytes 16-byte aligned and with 4 bytes
+        of slack behind them (the span hash reads whole dwords).  Returns ``(n, nbytes, d_offs, el,
+        d_bytes)``: the blocks, their bytes, and the three parts on the device."""
         import torch
 
-        cache, pool, ring, saved, state = self.cache, self.pool, self.ring, self.saved, self.state
         n = len(offsets) - 1
         nbytes = int(offsets[-1]) if n else 0
-        dev = torch.device("cuda", self.device)
-        # the one upload: offsets | eligible | bytes (the span hash reads whole dwords: 4 bytes of slack)
         o_end = 8 * (n + 1)
         e_end = o_end + n
         b_beg = e_end + (-e_end) % 16
@@ -1069,19 +1145,29 @@ class ResidentChain(metaclass=_PolicyKeywords):
         host[:o_end] = offsets.view(np.uint8)
         host[o_end:e_end] = 1 if eligible is None else eligible != 0
         host[b_beg:b_beg + nbytes] = data[:nbytes]
-        up = _to_device(host, dev)
-        d_offs, el, d_bytes = up[:o_end].view(torch.int64), up[o_end:e_end], up[b_beg:]
-        self.calls += 1
+        up = _to_device(host, torch.device("cuda", self.device))
+        return n, nbytes, up[:o_end].view(torch.int64), up[o_end:e_end], up[b_beg:]
 
+    def _extras(self, buf):
+        """The policies' bytes of the run's one read, side by side at the buffer's ``extra`` offset
+        (``buf``: the buffer from there on, on the device or as read): the cache's, then the pool's."""
+        cut = self._cache_room.extra_bytes
+        return buf[:cut], buf[cut:cut + self._pool_room.extra_bytes]
+
+    def _queue(self, n, nbytes, d_offs, el, d_bytes):
+        """Everything a run queues on the device behind :meth:`_upload`: split, decode and the checks
+        with the chain's scalars, :func:`_queue_run`, ``pz_dev_block_cycle`` and the policies' sums.
+        Returns the run, a dict: ``d`` (:func:`_decode_check`'s), ``q`` (:func:`_queue_run`'s), the
+        ``lag`` it took, ``log`` (the scan's hash log) and ``vote`` / ``take`` (the two landings' columns)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
         lag = int(self.lag)
         ljs, lsr = self.chain_scalars()
         d = _decode_check(d_bytes, d_offs, n, ljs, lsr, 128, self._narr, self._table, dev, want_committee=True)
-        natt, blk, status = d["natt"], d["blk"], d["status"]
-        managed = self.cache_policy != "fixed"
-        grows = self.pool_policy == "grow"
-        # the policies' extras side by side: the cache's two sums (16 bytes), then the pool's need (2 x 7 x 8)
-        x_pool = 16 if managed else 0
-        q = _queue_run(d, nbytes, _fold_eligible(blk["status"], el), saved, 8, extra=x_pool + (112 if grows else 0))
+        natt, blk = d["natt"], d["blk"]
+        q = _queue_run(d, nbytes, _fold_eligible(blk["status"], el), self.saved, 8,
+                       extra=self._cache_room.extra_bytes + self._pool_room.extra_bytes)
         p = _lib.dptr
         base = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
         log = torch.empty(int(lib.dll.pz_block_cycle_scratch_bytes(n, natt)), dtype=torch.uint8, device=dev)
@@ -1096,65 +1182,59 @@ class ResidentChain(metaclass=_PolicyKeywords):
                                  vote0=vote[0].data_ptr(), vote1=vote[1].data_ptr(), take0=take[0].data_ptr(),
                                  take1=take[1].data_ptr(), walk=p(q["walk"]), base=p(base), result=p(q["result"]), log=p(log),
                                  flags=p(q["flags"]))
-        lib.call("pz_dev_block_cycle", ring._h, ctypes.byref(b), q["sh"])
-        if managed and natt:  # the oblique elements of the rows each landing tallies: they come along in the read
-            nobl = d["att"]["n_oblique"][:natt]
-            lands = torch.stack([(nobl * (vote[k, :natt] == ATT_PROCESSED)).sum() for k in (0, 1)])
-            q["word"][q["at"]["extra"]:q["at"]["extra"] + 16].copy_(lands.view(torch.uint8))
-        if grows and natt:  # what each landing's append would add to the pool's counts: likewise
-            need = pool.need_columns(d["att"], natt, status.contiguous(), take[0], take[1])
-            q["word"][q["at"]["extra"] + x_pool:].copy_(need.view(torch.uint8).reshape(-1))
-        empty = (0, 0, int(bool(self.has_candidate)), int(self.candidate_slot) if self.has_candidate else 0, _NO_T, 0, 0, lag)
-        (_, _, has, cslot, t_index, t_rank, t_slot, lag_out), panic, out = _read_run(q, d, saved, empty)
+        lib.call("pz_dev_block_cycle", self.ring._h, ctypes.byref(b), q["sh"])
+        if natt:  # the policies' sums over the rows each landing takes: they come along in the read
+            x_cache, x_pool = self._extras(q["word"][q["at"]["extra"]:])
+            self._cache_room.queue(x_cache, d["att"]["n_oblique"][:natt], vote[:, :natt])
+            self._pool_room.queue(x_pool, d["att"], natt, d["status"].contiguous(), take)
+        return {"d": d, "q": q, "lag": lag, "log": log, "vote": vote, "take": take}
+
+    def _read(self, run):
+        """The one host read of a queued run (:func:`_read_run`).  Adds to the run ``record`` (the
+        scan's result record) and, for each landing, ``oblique`` and ``need`` (the policies' sums);
+        returns ``(out, panic)``, ``out`` as far as the read fills it."""
+        empty = (0, 0, int(bool(self.has_candidate)), int(self.candidate_slot) if self.has_candidate else 0, _NO_T, 0, 0, run["lag"])
+        run["record"], panic, out = _read_run(run["q"], run["d"], self.saved, empty)
+        t_index, lag_out = run["record"][4], run["record"][7]
         out["t_index"], out["lag"] = None if t_index == _NO_T else t_index, lag_out
-        nlog = 129 + out["ncand"]  # the log entries the tallies read
-        obl = [int(x) for x in np.frombuffer(q["extra_host"][:16].tobytes(), dtype=np.uint64)] if managed else None
-        pneed = np.frombuffer(q["extra_host"][x_pool:].tobytes(), dtype=np.uint64).reshape(2, 7) if grows else None
-        counted = [False]  # the run's log is counted in _slots_ub
+        x_cache, x_pool = self._extras(run["q"]["extra_host"])
+        run["oblique"], run["need"] = self._cache_room.parse(x_cache), self._pool_room.parse(x_pool)
+        return out, panic
 
-        def room(phase):  # before a landing's tally: the bounds fit, or the policy makes them
-            need = obl[phase] + (0 if counted[0] else nlog - (129 if self._ring_counted else 0))
-            if self._slots_ub + need > cache.slot_cap:
-                if self.cache_policy == "retire":  # the kept entries and the log's new ones are the log's hashes
-                    cache.retain(log[:32 * nlog])
-                    self.cache_retains += 1
-                    self._slots_ub, need = nlog, obl[phase]
-                if self._slots_ub + need > cache.slot_cap:
-                    cache.reserve(max(self._slots_ub + need, min(2 * cache.slot_cap, 1 << 30)), device_form=True)
-                    self.cache_grows += 1
-            self._slots_ub += need
-            counted[0] = True
+    def _land(self, run, phase):
+        """calculateBlockVoteCache and processedAttestations of one side of stateRecalc (``phase`` 0:
+        the rows before it, 1: behind it), each behind its policy's room."""
+        d, natt, log = run["d"], run["d"]["natt"], run["log"]
+        self._cache_room.fit(run["oblique"][phase], 129 + run["record"][1], log)  # (the log entries the tallies read)
+        self.cache.tally_columns(d["att"], natt, run["vote"][phase], d["committee"], d["parents_start"], log, self._members,
+                                 self._table[3], self.state.balance)
+        self._pool_room.fit(run["need"][phase])
+        self.pool.append_columns(d["att"], natt, d["status"].contiguous(), d["committee"], take=run["take"][phase])
 
-        def land(phase):  # calculateBlockVoteCache and processedAttestations of one side of stateRecalc
-            if managed:
-                room(phase)
-            cache.tally_columns(d["att"], natt, vote[phase], d["committee"], d["parents_start"], log, self._members,
-                                self._table[3], state.balance)
-            if grows:
-                self._pool_room([int(x) for x in pneed[phase]])
-            pool.append_columns(d["att"], natt, status.contiguous(), d["committee"], take=take[phase])
-
-        if not panic:
-            try:  # from here on the ring has rolled and the set has grown: an error leaves the objects ahead of the carry
+    def _land_run(self, run):
+        """The landing of a read run whose gate did not panic: the rows before stateRecalc, with a
+        transition block stateRecalc and the rows behind it, then the carry."""
+        _, ncand, has, cslot, t_index, t_rank, t_slot, lag_out = run["record"]
+        natt, log = run["d"]["natt"], run["log"]
+        try:  # from here on the ring has rolled and the set has grown: an error leaves the objects ahead of the carry
+            self._cache_room.begin()
+            if natt:
+                self._land(run, 0)
+            chain_pair = self._chain
+            if t_index != _NO_T:
+                window = log[32 * (1 + t_rank):32 * (1 + t_rank + 128)]  # the promoted ActiveState's RecentBlockHashes
+                pre = self._cand
+                scal = _recalc_resident(self.pool, self.cache, self.state, window, 128, t_slot)["scalars"]
+                self._cand = (int(scal[2]), int(scal[0]))
+                chain_pair = pre  # what the chain keeps until T's states are promoted
                 if natt:
-                    land(0)
-                chain_pair = self._chain
-                if t_index != _NO_T:
-                    window = log[32 * (1 + t_rank):32 * (1 + t_rank + 128)]  # the promoted ActiveState's RecentBlockHashes
-                    pre = self._cand
-                    scal = _recalc_resident(pool, cache, state, window, 128, t_slot)["scalars"]
-                    self._cand = (int(scal[2]), int(scal[0]))
-                    chain_pair = pre  # what the chain keeps until T's states are promoted
-                    if natt:
-                        land(1)
-            except BaseException:
-                self.spent = True
-                raise
-            self.has_candidate, self.candidate_slot, self.lag = bool(has), cslot, lag_out
-            self._chain = chain_pair if lag_out else None
-            # the next ring is log entries [ncand, ncand + 129): counted iff this run's log was, or nothing rolled
-            self._ring_counted = counted[0] or (self._ring_counted and out["ncand"] == 0)
-        return _run_outputs(out, d, q["walk"], q["block_status"], q["block_hash"], log, want_digests), panic
+                    self._land(run, 1)
+        except BaseException:
+            self.spent = True
+            raise
+        self.has_candidate, self.candidate_slot, self.lag = bool(has), cslot, lag_out
+        self._chain = chain_pair if lag_out else None
+        self._cache_room.end(ncand)
 
     def process_all(self, data, offsets, eligible=None, want_digests=False):
         """:meth:`process_serialized` from ``stop`` on until the bytes are used up: a list of its

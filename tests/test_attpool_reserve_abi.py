@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from prysm_amd import _lib
+from test_blockcycle_abi import check_resident_chain_init
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {"pz_att_pool_capacity": "int", "pz_dev_att_pool_reserve": "int", "pz_att_pool_reserve": "int",
@@ -112,8 +113,7 @@ def test_python_face():
     assert "reserve" in pending.DevicePendingAttestations.view.__doc__
     RC = blockchain.ResidentChain
     assert RC.POOL_POLICIES == ("fixed", "grow")
-    assert list(inspect.signature(RC.__init__).parameters) == ["self", "cache", "pool", "ring", "saved", "state",
-                                                               "shard_and_committees", "device"]
+    check_resident_chain_init(RC)
     assert inspect.signature(RC.from_state).parameters["pool_policy"].default == "fixed"
     # an unknown policy is refused before any object is made (the arguments are never looked at)
     with pytest.raises(_lib.PzError) as e:

@@ -115,13 +115,25 @@ def test_argument_errors_are_einval():
     assert not host.any()
 
 
+def check_resident_chain_init(RC):
+    """ResidentChain's constructor as callers know it: the seven positional arguments in their order,
+    ``device`` defaulting to 0, then exactly the two policies, keyword-only and "fixed" by default,
+    on a plain class."""
+    params = list(inspect.signature(RC.__init__).parameters.values())
+    assert [p.name for p in params[:8]] == ["self", "cache", "pool", "ring", "saved", "state", "shard_and_committees", "device"]
+    assert all(p.kind is inspect.Parameter.POSITIONAL_OR_KEYWORD for p in params[:8])
+    assert [p.default for p in params[:8]] == [inspect.Parameter.empty] * 7 + [0]
+    assert [(p.name, p.kind, p.default) for p in params[8:]] == [("cache_policy", inspect.Parameter.KEYWORD_ONLY, "fixed"),
+                                                                 ("pool_policy", inspect.Parameter.KEYWORD_ONLY, "fixed")]
+    assert type(RC) is type
+
+
 def test_python_face_exists():
     from prysm_amd import blockchain
     sig = inspect.signature(blockchain.ResidentChain.process_serialized)
     assert list(sig.parameters) == ["self", "data", "offsets", "eligible", "want_digests"]
     assert list(inspect.signature(blockchain.ResidentChain.process_all).parameters) == ["self", "data", "offsets", "eligible",
                                                                                         "want_digests"]
-    assert list(inspect.signature(blockchain.ResidentChain.__init__).parameters) == ["self", "cache", "pool", "ring", "saved", "state",
-                                                                                     "shard_and_committees", "device"]
+    check_resident_chain_init(blockchain.ResidentChain)
     # the walk's entry points keep their pinned parameter lists
     assert list(inspect.signature(blockchain.walk_serialized_blocks).parameters)[:4] == ["cache", "pool", "ring", "data"]
