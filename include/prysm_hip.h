@@ -1272,6 +1272,80 @@ int pz_dev_block_set_insert_walked(pz_block_set* set, const uint8_t* d_block_has
                                    const uint32_t* d_flags /* optional */, uint64_t nblocks, uint64_t* d_count_out /* optional */,
                                    void* stream);
 
+/* ---- H: the attestation store batch of a run of blocks --------------------------------------------
+ * What blockProcessing writes to the database for every attestation it accepts (blockchain/
+ * service.go:281-301): saveAttestation stores the record under Attestation.Key() (core.go:650-658,
+ * types/attestation.go:61-77) and saveAttestationHash appends Attestation.Hash() (types/attestation.go:
+ * 50-59) to the block's AttestationHashes list (core.go:745-760).  The batch of a run is selected,
+ * hashed and encoded on the device from the columns the run's other entry points left there.
+ *
+ * Row r of block j = att_block[r] is SAVED when j < *stop (NULL: nblocks; a deferred block is written
+ * by the call that processes it), block_status[j] == PZ_OK (the decoder's status with every record's
+ * folded in: a block with a non-canonical block or record is refused whole), parent_ok[j] != 0
+ * (service.go:261-269), att_status[r] == PZ_ATT_PROCESSED and rec_status[r] == PZ_OK (NULL: all).  The
+ * rule does not read CanProcessBlock (tested at service.go:308, after the saves at :288-297) nor the
+ * outcome of the block's last attestation (:304): blockstore_dev.h states it once.
+ *
+ * select, with m the number of saved rows: rows[i] (i < m) = the i-th saved row in ascending order,
+ * span[2 i], span[2 i + 1] = its att_beg, att_end -- the bytes saveAttestation writes, since only
+ * canonical records get here -- first[j] (j <= nblocks) = the number of saved rows before row
+ * att_first[j], so that block j's are [first[j], first[j + 1]), and *count = m.  Entries of rows and
+ * span past m are not written.
+ * digests, over the m rows select left: hash[32 i ..] = Attestation.Hash() = blake2b.Sum512 of
+ * bytes[span[2 i], span[2 i + 1]) truncated to 32 bytes (4 readable bytes past `bytes`, the span
+ * hash's contract); key[32 i ..] = Attestation.Key() of row rows[i] of the natt rows of `a`, as
+ * pz_dev_attestation_keys makes it (a rows[i] >= natt gets a zero key); lists[34 i ..] = 0a 20 |
+ * hash[i], the proto3 encoding of one AttestationHashes.attestation_hash element (messages.proto:
+ * 128-130): block j's appended bytes are lists[34 first[j] .. 34 first[j + 1]).  Exactly 34 m bytes of
+ * lists are written.
+ *
+ * select is four dependent launches on the caller's stream (size, scan, write, first: the
+ * reduce-then-scan of DESIGN.md §3), digests three independent ones (the span hash, the key kernel
+ * through the row list, the entries as whole dwords); no workgroup waits for another, the host reads
+ * nothing.  PZ_EINVAL, before any launch -- select: a NULL batch; nblocks >= 2^31; natt >= 2^32; with
+ * nblocks > 0 and natt > 0 a NULL att_first, block_status, parent_ok, att_block, att_status, att_beg,
+ * att_end, rows, span, first or count; (device form) a NULL or misaligned d_scratch, a span that is
+ * not 16-byte aligned, any other pointer that is not aligned to its element.  digests: a NULL batch;
+ * m > natt; natt >= 2^32; with m > 0 a NULL bytes, rows, span, key, hash, lists or `a`, offsets of `a`
+ * without their data column; (device form) a span, key or hash that is not 16-byte aligned, rows or
+ * lists not 4-byte aligned; (host form) a rows[i] >= natt, a span that is inverted or leaves
+ * [0, nbytes), offsets of `a` that are not monotone.  nblocks == 0 or natt == 0 (select) and m == 0
+ * (digests) launch nothing; the host form of select then sets *count and first[0 .. nblocks] to 0. */
+typedef struct pz_block_store_batch {   /* every member a pointer or a uint64_t */
+  uint64_t nblocks;
+  const uint64_t* att_first;     /* nblocks + 1: pz_block_cols_out.att_first */
+  const int32_t*  block_status;  /* nblocks: pz_block_cols_out.status with the records' statuses folded in */
+  const uint8_t*  parent_ok;     /* nblocks: pz_block_parents_batch.parent_ok */
+  const uint64_t* stop;          /* optional, one word: pz_block_cycle_batch.result (word 0), read on the device */
+  uint64_t natt;
+  const uint32_t* att_block;     /* natt: pz_block_cols_out.att_block */
+  const int32_t*  att_status;    /* natt: pz_att_check_batch.status */
+  const int32_t*  rec_status;    /* optional, natt: pz_attestation_cols_out.status */
+  const uint64_t* att_beg;       /* natt: pz_block_cols_out.att_beg */
+  const uint64_t* att_end;       /* natt: pz_block_cols_out.att_end */
+  uint32_t* rows;                /* room for natt; m written by select, read by digests */
+  uint64_t* span;                /* room for natt x 2; m x 2 written by select, read by digests */
+  uint64_t* first;               /* nblocks + 1, select */
+  uint64_t* count;               /* one word, select: m */
+  const uint8_t* bytes;          /* digests: the received blocks' bytes the spans point into */
+  uint64_t nbytes;               /* the host form uploads this many */
+  uint8_t* key;                  /* digests: m x 32 */
+  uint8_t* hash;                 /* digests: m x 32 */
+  uint8_t* lists;                /* digests: 34 m */
+} pz_block_store_batch;
+/* The bytes of select's d_scratch (no reference counterpart). */
+uint64_t pz_block_store_scratch_bytes(uint64_t nblocks, uint64_t natt);
+/* Which rows service.go:281-301 saves, device pointers, on the caller's stream, asynchronous. */
+int pz_dev_block_store_select(const pz_block_store_batch* b, void* d_scratch, void* stream);
+/* Key, Hash and the list entries of the saved rows (core.go:650-658, :745-760), device pointers (`a`
+ * holds device pointers too), on the caller's stream, asynchronous. */
+int pz_dev_block_store_digests(const pz_block_store_batch* b, const pz_attestation_cols* a, uint64_t m, void* stream);
+/* Which rows service.go:281-301 saves, host pointers (any alignment), synchronous. */
+int pz_block_store_select(const pz_block_store_batch* b);
+/* Key, Hash and the list entries of the saved rows (core.go:650-658, :745-760), host pointers (any
+ * alignment), synchronous. */
+int pz_block_store_digests(const pz_block_store_batch* b, const pz_attestation_cols* a, uint64_t m);
+
 /* ---- R: ActiveState.PendingAttestations resident on the device --------------------------------
  * The attestations a block contributes (processedAttestations, blockchain/service.go:280-301)
  * become ActiveState.PendingAttestations (computeNewActiveState, core.go:223-237) and feed the

@@ -151,6 +151,11 @@ SIGNATURES = {
     "pz_dev_block_parents": [vp, vp, vp, vp],
     "pz_block_parents": [vp, vp],
     "pz_dev_block_set_insert_walked": [vp, vp, vp, vp, u64, vp, vp],
+    "pz_block_store_scratch_bytes": [u64, u64],
+    "pz_dev_block_store_select": [vp, vp, vp],
+    "pz_dev_block_store_digests": [vp, vp, u64, vp],
+    "pz_block_store_select": [vp],
+    "pz_block_store_digests": [vp, vp, u64],
     "pz_att_pool_new": [vp, ctypes.c_int, vp],
     "pz_att_pool_free": [vp],
     "pz_att_pool_scratch_bytes": [u64],
@@ -369,6 +374,15 @@ class BlockParentsBatch(ctypes.Structure):
     ]
 
 
+class BlockStoreBatch(ctypes.Structure):
+    """Mirror of ``pz_block_store_batch`` (include/prysm_hip.h)."""
+    _fields_ = [
+        ("nblocks", u64), ("att_first", vp), ("block_status", vp), ("parent_ok", vp), ("stop", vp), ("natt", u64),
+        ("att_block", vp), ("att_status", vp), ("rec_status", vp), ("att_beg", vp), ("att_end", vp), ("rows", vp), ("span", vp),
+        ("first", vp), ("count", vp), ("bytes", vp), ("nbytes", u64), ("key", vp), ("hash", vp), ("lists", vp),
+    ]
+
+
 class RecalcBatch(ctypes.Structure):
     """Mirror of ``pz_recalc_batch`` (include/prysm_hip.h)."""
     _fields_ = [
@@ -418,7 +432,7 @@ _RESTYPES = {"pz_last_error": ctypes.c_char_p, "pz_chain_free": None, "pz_set_se
              "pz_att_pool_free": None, "pz_att_pool_scratch_bytes": u64, "pz_att_pool_need_scratch_bytes": u64,
              "pz_recent_hashes_free": None, "pz_block_walk_scratch_bytes": u64,
              "pz_block_cycle_scratch_bytes": u64,
-             "pz_block_set_free": None, "pz_block_parents_scratch_bytes": u64,
+             "pz_block_set_free": None, "pz_block_parents_scratch_bytes": u64, "pz_block_store_scratch_bytes": u64,
              "pz_recalc_state_free": None, "pz_state_recalc_scratch_bytes": u64,
              "pz_wire_committees_bound": u64, "pz_wire_committees_scratch_bytes": u64,
              "pz_crystallized_state_bound": u64, "pz_crystallized_state_scratch_bytes": u64, "pz_active_state_bound": u64,

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "att_cols.h"
+#include "attdigest.h"
 #include "blake2b_dev.h"
 #include "resident.h"
 
@@ -158,11 +159,24 @@ struct KeyArgs {
 // ------------------------------------------------------------------------------------------
 constexpr int kKeyPieces = 6;
 
-extern "C" __global__ void __launch_bounds__(kThreads) pz_att_key_kernel(KeyArgs a) {
+// kList false: output row o is the Key of row o of the columns (pz_[dev_]attestation_keys).  true: of
+// row list[o] of the columns' nsrc rows (launch_att_keys_rows: the attestation store's saved rows,
+// blockstore.hip); a list entry that names no row gets a zero key.  A template, so that both compile
+// the one text and the plain form compiles to what it did as a plain kernel.
+template <bool kList>
+__global__ void __launch_bounds__(kThreads) pz_att_key_kernel(KeyArgs a, const uint32_t* list, uint64_t nsrc) {
   __shared__ uint32_t rows[kThreads * kRowWords];
-  const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= a.n) return;  // no block-wide barrier below: lanes only touch their own row
-  uint8_t* out = a.out + i * a.out_bytes;
+  const uint64_t o = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (o >= a.n) return;  // no block-wide barrier below: lanes only touch their own row
+  uint8_t* out = a.out + o * a.out_bytes;
+  uint64_t i = o;
+  if constexpr (kList) {
+    i = list[o];
+    if (i >= nsrc) {
+      store_zero(out, a.out_bytes);
+      return;
+    }
+  }
   if (a.rec_status && a.rec_status[i] != PZ_OK) {
     store_zero(out, a.out_bytes);
     return;
@@ -372,7 +386,8 @@ hipError_t launch_att_keys(const pz_attestation_cols& a, uint64_t n, const int32
                            uint32_t out_bytes, hipStream_t s) {
   KeyArgs k{a.slot, a.shard_id, a.shard_block_hash, a.shard_block_hash_offs, a.oblique_parent_hashes,
             a.oblique_offs, a.oblique_first, rec_status, n, out, out_bytes};
-  hipLaunchKernelGGL(pz_att_key_kernel, dim3((uint32_t)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, k);
+  hipLaunchKernelGGL(pz_att_key_kernel<false>, dim3((uint32_t)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, k,
+                     (const uint32_t*)nullptr, (uint64_t)0);
   return hipGetLastError();
 }
 
@@ -405,6 +420,24 @@ int check_key_cols(const pz_attestation_cols& a, uint64_t n) {
 }
 
 }  // namespace
+
+// attdigest.h: Key through a row list, for the attestation store (blockstore.hip).
+hipError_t launch_att_keys_rows(const pz_attestation_cols& a, uint64_t nsrc, const uint32_t* list, uint64_t n, uint8_t* out,
+                                hipStream_t s) {
+  KeyArgs k{a.slot, a.shard_id, a.shard_block_hash, a.shard_block_hash_offs, a.oblique_parent_hashes,
+            a.oblique_offs, a.oblique_first, nullptr, n, out, 32};
+  hipLaunchKernelGGL(pz_att_key_kernel<true>, dim3((uint32_t)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, k, list, nsrc);
+  return hipGetLastError();
+}
+
+int check_att_key_cols(const pz_attestation_cols* a, uint64_t n, bool host_form) {
+  if (!a) return fail(PZ_EINVAL, "columns are null");
+  if (a->shard_block_hash_offs && !a->shard_block_hash) return fail(PZ_EINVAL, "shard_block_hash is null");
+  if (a->oblique_first && (!a->oblique_offs || !a->oblique_parent_hashes))
+    return fail(PZ_EINVAL, "oblique_first without oblique_offs / oblique_parent_hashes");
+  return host_form ? check_key_cols(*a, n) : PZ_OK;
+}
+
 }  // namespace pz
 
 using namespace pz;

@@ -250,12 +250,17 @@ __device__ __forceinline__ void load_block_csr(const uint8_t* p, uint64_t rem, u
 // Message i is msgs[begs[i], ends[i]): CSR passes (offsets, offsets + 1); the span form
 // (launch_b2b_spans) hashes messages that overlap or leave gaps, e.g. attestation records
 // inside their blocks' bytes.
-extern "C" __global__ void __launch_bounds__(256)
+// kStride 1: begs and ends are columns; 2: they point into one column of (beg, end) pairs, message i
+// being msgs[span[2 i], span[2 i + 1]) (launch_b2b_span_pairs: the attestation store's compacted
+// spans, blockstore.hip).  A template, so that both compile the one text and the columns' form
+// compiles to what it did as a plain kernel.
+template <int kStride>
+__global__ void __launch_bounds__(256)
 pz_b2b_csr_kernel(const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ begs,
                   const uint64_t* __restrict__ ends, uint64_t n, uint8_t* __restrict__ out, uint32_t out_bytes) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint64_t beg = begs[i], end = ends[i];
+  const uint64_t beg = begs[kStride * i], end = ends[kStride * i];
   const uint64_t len = end - beg;
   const uint64_t nblocks = len == 0 ? 1 : (len + 127) / 128;
   uint64_t h[8];
@@ -429,7 +434,7 @@ hipError_t launch_b2b_csr(const uint8_t* msgs, const uint64_t* offsets, uint64_t
                           uint32_t out_bytes, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   const uint64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL(pz_b2b_csr_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, msgs,
+  hipLaunchKernelGGL(pz_b2b_csr_kernel<1>, dim3((uint32_t)blocks), dim3(256), 0, stream, msgs,
                      offsets, offsets + 1, n, out, out_bytes);
   return hipGetLastError();
 }
@@ -437,8 +442,16 @@ hipError_t launch_b2b_csr(const uint8_t* msgs, const uint64_t* offsets, uint64_t
 hipError_t launch_b2b_spans(const uint8_t* msgs, const uint64_t* begs, const uint64_t* ends, uint64_t n, uint8_t* out,
                             uint32_t out_bytes, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(pz_b2b_csr_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, msgs, begs, ends, n,
+  hipLaunchKernelGGL(pz_b2b_csr_kernel<1>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, msgs, begs, ends, n,
                      out, out_bytes);
+  return hipGetLastError();
+}
+
+hipError_t launch_b2b_span_pairs(const uint8_t* msgs, const uint64_t* span, uint64_t n, uint8_t* out, uint32_t out_bytes,
+                                 hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(pz_b2b_csr_kernel<2>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, msgs, span, span + 1, n, out,
+                     out_bytes);
   return hipGetLastError();
 }
 

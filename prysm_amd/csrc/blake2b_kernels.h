@@ -11,6 +11,9 @@ hipError_t launch_b2b_csr(const uint8_t* msgs, const uint64_t* offsets, uint64_t
 // message i = msgs[begs[i], ends[i]) (spans may overlap; 4 readable bytes past each end)
 hipError_t launch_b2b_spans(const uint8_t* msgs, const uint64_t* begs, const uint64_t* ends, uint64_t n, uint8_t* out,
                             uint32_t out_bytes, hipStream_t stream);
+// the same with the spans as pairs: message i = msgs[span[2 i], span[2 i + 1]) (span 16-byte aligned)
+hipError_t launch_b2b_span_pairs(const uint8_t* msgs, const uint64_t* span, uint64_t n, uint8_t* out, uint32_t out_bytes,
+                                 hipStream_t stream);
 // One processAttestation message: its 10-byte header, where its 64 signed parent ids are
 // (trail[wstart, wstart + nw), then 64 - nw oblique ids at var[vo..]) and its ShardBlockHash
 // (sl bytes right after those ids).  32 bytes, appended by the walk into pinned memory.
